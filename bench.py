@@ -6,8 +6,15 @@ one full CoulForce evaluation (forces + energy: flux charges, Ewald real space w
 reciprocal k-sum, self term, exclusion correction, dE/dq chain rule) on the GPU through
 the C-ABI, plus harmonic O-H/H-H restraints and the integrator update (torch, plumbing).
 
+A plain run sets up, warms up (W steps, then min(K, 100) more so that the timed region covers
+the steps of the trajectory it always has), times the K steps and prints the result line (with
+--dump-outputs DIR it also writes what the last timed step computed).  --full adds every other
+measurement to the line: the per-kernel breakdown and roofline, the force-evaluation, harness
+and graph-replay passes, the exact k-sum comparison, the host and OpenMM-buffer boundaries and
+the CPU baseline.
+
 Single node, one process per GPU:
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 Multi-GPU = atom decomposition of one system (strong scaling): per step one RCCL
@@ -38,6 +45,7 @@ HBM_PEAK_GBS = 8000.0
 K_OH, R_OH0 = 345000.0, 0.09572      # harness restraints (kJ/mol/nm^2, nm)
 K_HH, R_HH0 = 230000.0, 0.15139
 KB = 0.0083144626                     # kJ/mol/K
+SETTLE_STEPS = 100                    # cap of a plain run's untimed pass between warm-up and timed region
 
 
 def log(*a):
@@ -182,6 +190,26 @@ def pmc_traffic(config, world, phase, precision, pair_list):
     return int(total), os.path.relpath(files[-1], ROOT)
 
 
+def dump_outputs(path, rank, world, lo, hi, pos, vel, frc, energy):
+    """What the last timed step handed back, as float64 .npy files (rank 0 writes): forces (the
+    CoulForce evaluation at the step's positions, kJ/mol/nm), energy (kJ/mol, one element),
+    positions (nm) and velocities (nm/ps) as integrated up to that evaluation.  Whole arrays:
+    the largest configuration (C5, 768 000 atoms) is 3 x 18.4 MB.  On several ranks each holds the
+    forces and velocities of its owned atoms [lo, hi) only: the owned rows are summed over ranks."""
+    f, v = frc, vel
+    if world > 1:
+        own = torch.zeros(len(pos), 1, dtype=pos.dtype, device=pos.device)
+        own[lo:hi] = 1.0
+        f, v = frc * own, vel * own
+        dist.all_reduce(f)
+        dist.all_reduce(v)
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("forces", f), ("energy", energy), ("positions", pos), ("velocities", v)):
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -194,13 +222,20 @@ def main():
                     help="ES kernel width for --kspace-algo 2 (0 = 14, or 8 with --precision mixed)")
     ap.add_argument("--precision", default="double", choices=["double", "mixed"],
                     help="mixed: fp32 direct-space pair kernel (fp32 force / fp64 energy accumulation), W=8 grid")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (kernel breakdown and roofline, force-evaluation, "
+                         "harness and graph passes, exact k-sum comparison, host / OpenMM-buffer boundaries, CPU "
+                         "baseline); without it: set-up, warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (forces, energy and the "
+                         "integrated positions and velocities) as DIR/<name>.npy, float64")
     ap.add_argument("--no-exact-compare", action="store_true",
-                    help="skip timing the exact k-sum path beside the grid path")
+                    help="with --full: skip timing the exact k-sum path beside the grid path")
     ap.add_argument("--cpu-k-sample", type=int, default=0,
                     help="k-vectors of the CPU-baseline sample (0 = 10%% of K_half)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-kernel-timing", action="store_true",
-                    help="no per-kernel HIP events in the timed steps (measures their overhead; no roofline)")
+                    help="with --full: no per-kernel HIP events in the timed steps (measures their overhead)")
     ap.add_argument("--graph", type=int, default=0,
                     help="1: replay each step's CoulForce launches as a captured hipGraph (cf_set_graph) in the "
                          "timed region")
@@ -281,18 +316,27 @@ def main():
     # library's stream, with the second stream off (cf_set_overlap) so that each phase's time is
     # its own, not stretched by kernels of the other chain sharing the CUs.  Those event records
     # cost ~10% of a step, so the timed region below brackets only the dominant kernel.
+    # (--full only.  A plain run takes the same steps without events or timing, at most SETTLE_STEPS
+    # of them: the timed region then covers the same steps of the trajectory as with --full.  The
+    # first steps from the lattice start are not the steady state -- a 20-step region right after 5
+    # warm-up steps read 0.441 ms against 0.427 ms one pass later, 0.43 ms over 2000 steps.)
     HOT = ("direct_pairs", "grid_spread", "grid_interp", "kspace_sfac", "kspace_force")
-    kern.kernel.set_overlap(False)
-    kern.kernel.set_timing(True)
-    for _ in range(args.steps):
-        energy = step(True)
-    torch.cuda.synchronize()
-    timing_all = kern.kernel.timing()
-    kern.kernel.set_timing(False)
-    kern.kernel.set_overlap(True)   # the library's default
-    ms_eval = float(np.mean([a.elapsed_time(b) for a, b in ev])) if ev else float("nan")
-    per_step = {k: v[0] / args.steps for k, v in timing_all.items()}   # amortized (list phases are not every step)
-    dom = max((k for k in HOT if per_step.get(k, 0.0) > 0), key=lambda k: per_step[k], default=None)
+    dom = None
+    if not args.full:
+        for _ in range(min(args.steps, SETTLE_STEPS)):
+            energy = step(False)
+    else:
+        kern.kernel.set_overlap(False)
+        kern.kernel.set_timing(True)
+        for _ in range(args.steps):
+            energy = step(True)
+        torch.cuda.synchronize()
+        timing_all = kern.kernel.timing()
+        kern.kernel.set_timing(False)
+        kern.kernel.set_overlap(True)   # the library's default
+        ms_eval = float(np.mean([a.elapsed_time(b) for a, b in ev])) if ev else float("nan")
+        per_step = {k: v[0] / args.steps for k, v in timing_all.items()}   # amortized (list phases are not every step)
+        dom = max((k for k in HOT if per_step.get(k, 0.0) > 0), key=lambda k: per_step[k], default=None)
 
     # timed region: K steps, barrier + synchronize on both sides, max over ranks
     if args.graph and world == 1:
@@ -319,6 +363,41 @@ def main():
     builds1, evals1 = kern.kernel.neighbor_stats()
     fb1 = kern.kernel.fallback_stats()
     kern.kernel.set_timing(False)
+    ms_step = elapsed / args.steps * 1e3
+    ns_day = 86.4 / ms_step * (dt / 0.001)
+    w_grid = kern.kernel.grid_width() if args.kspace_algo == 2 else 0   # the library's choice (0: its default)
+    kern.synchronize()   # energy all-reduce still in flight (multi-rank)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, lo, hi, pos, vel, frc, energy)
+
+    def result_line(e_final):
+        return {
+            "metric": METRIC, "value": round(ns_day, 4), "unit": "ns/day", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_step, 4), "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None,
+            "dtype": "f64" if args.precision == "double" else "f32 pairs / f64 rest (mixed)", "data": "synthetic",
+            "config": {"workload": f"{args.config}: periodic flexible charge-flux water box, {n} atoms, Ewald "
+                                   f"rc={force.getCutoffDistance()} nm tol={force.getEwaldErrorTolerance()} "
+                                   f"(alpha {alpha:.5f}, kmax {kmax[0]}, K_half {k_half}), velocity Verlet dt="
+                                   f"{dt * 1000:g} fs, " + ("fp64" if args.precision == "double" else
+                                                            "mixed precision (fp32 pair kernel)"),
+                       "atoms": n, "kmax": list(kmax), "k_half": k_half,
+                       "neighbor_skin_nm": args.neighbor_skin, "handover": args.handover, "variants": args.variants,
+                       "kspace": {0: "exact k-sum, fp64 MFMA", 1: "exact k-sum, VALU",
+                                  2: f"grid (ES kernel W={w_grid}, pruned DFT), same k-set"}[args.kspace_algo],
+                       "nlist_builds_in_timed_steps": f"{builds1 - builds0}/{evals1 - evals0}",
+                       "fp64_rescan_fallbacks_in_timed_steps": int(fb1[0] - fb0[0]),
+                       "parallelism": f"atom-decomposition x{world}" + (" (RCCL all-reduce of S(k))" if world > 1 else "")},
+            "energy_kj_mol": e_final,
+        }
+
+    if not args.full:
+        # a plain run ends here: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(result_line(energy.item())), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # force-evaluation pass (after the timed region, not part of it): K more MD steps with two
     # torch events around each execute (the library's stream is torch's current stream) and no
     # library timing at all -> ms_per_force_eval without instrumentation
@@ -364,9 +443,7 @@ def main():
         kern.kernel.set_graph(False)
     kern.synchronize()   # energy all-reduce still in flight (multi-rank)
     e_final = energy.item()
-    ms_step = elapsed / args.steps * 1e3
     ms_eval_clean = ms_step - ms_harness
-    ns_day = 86.4 / ms_step * (dt / 0.001)
 
     per_launch = {k: (v[0] / v[1] if v[1] else 0.0) for k, v in timing_all.items()}   # isolated (breakdown pass)
     dom_isolated_ms = per_launch.get(dom) if dom is not None else None
@@ -385,7 +462,6 @@ def main():
     #  grid_interp   4 N W^3 fp64 VALU flops (two FMAs per grid value), bytes 8 ng^3 + 24 N W + 32 N
     #  kspace_sfac / kspace_force (exact path)  4 / 8 fp64 MFMA flops per atom x half-space k-vector
     # fraction of the roof = max(B / BW, F / P) / t; "bound" names the larger term
-    w_grid = kern.kernel.grid_width() if args.kspace_algo == 2 else 0   # the library's choice (0: its default)
     roofline, others = None, {}
     if dom is not None:
         p_c = pair_count(force, pos_np, box) * n_own / n
@@ -511,30 +587,14 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             log("[rank 0] timing CPU baseline sample ...")
             cpu = cpu_baseline(force, pos_np, box, args.cpu_k_sample or max(1, (k_half + 9) // 10))
-        out = {
-            "metric": METRIC, "value": round(ns_day, 4), "unit": "ns/day", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_step, 4), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None,
-            "dtype": "f64" if args.precision == "double" else "f32 pairs / f64 rest (mixed)", "data": "synthetic",
-            "config": {"workload": f"{args.config}: periodic flexible charge-flux water box, {n} atoms, Ewald "
-                                   f"rc={force.getCutoffDistance()} nm tol={force.getEwaldErrorTolerance()} "
-                                   f"(alpha {alpha:.5f}, kmax {kmax[0]}, K_half {k_half}), velocity Verlet dt="
-                                   f"{dt * 1000:g} fs, " + ("fp64" if args.precision == "double" else
-                                                            "mixed precision (fp32 pair kernel)"),
-                       "atoms": n, "kmax": list(kmax), "k_half": k_half,
-                       "neighbor_skin_nm": args.neighbor_skin, "handover": args.handover, "variants": args.variants,
-                       "kspace": {0: "exact k-sum, fp64 MFMA", 1: "exact k-sum, VALU",
-                                  2: f"grid (ES kernel W={w_grid}, pruned DFT), same k-set"}[args.kspace_algo],
-                       "nlist_builds_in_timed_steps": f"{builds1 - builds0}/{evals1 - evals0}",
-                       "fp64_rescan_fallbacks_in_timed_steps": int(fb1[0] - fb0[0]),
-                       "parallelism": f"atom-decomposition x{world}" + (" (RCCL all-reduce of S(k))" if world > 1 else "")},
+        out = result_line(e_final)
+        out.update({
             "ms_per_force_eval": round(ms_eval_clean, 4),
             "ms_per_harness_step": round(ms_harness, 4),
             "ms_per_force_eval_events": round(ms_eval_events, 4),
             "ms_per_force_eval_instrumented": round(ms_eval, 4),
             "graph_replay_ms_per_step": None if graph_ms is None else round(graph_ms, 4),
             "graph_stats": None if graph_ms is None else list(gstats),
-            "energy_kj_mol": e_final,
             "kernels_ms_per_step": {k: round(v, 4) for k, v in per_step.items()},
             "timing_note": (f"value: K steps with HIP events around {dom} launches only; ms_per_force_eval: "
                             f"ms_per_step minus ms_per_harness_step (K steps of the MD harness alone, wall clock); "
@@ -548,7 +608,7 @@ def main():
             "host_boundary": host,
             "openmm_gpu_buffers": openmm_buf,
             "cpu_baseline": cpu,
-        }
+        })
         if cpu:
             out["speedup_vs_cpu_force_eval"] = round(cpu["ms_per_force_eval"] / ms_eval_clean, 1)
         print(json.dumps(out), flush=True)

@@ -41,7 +41,7 @@ run() {   # name, log, seconds, command...
 cfgargs() { case $1 in c5) echo "--config C5 --precision mixed";; c3_mixed) echo "--precision mixed";; *) echo "";; esac; }
 # (the C5 CPU-baseline sample runs minutes without output: the box's silence guard would kill it)
 benchargs() { case $1 in c5) echo "--no-cpu-baseline";; *) echo "";; esac; }
-PROF_ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-exact-compare"
+PROF_ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-exact-compare"
 for st in "$@"; do
     case $st in
     tests|tests=*)
@@ -53,12 +53,12 @@ for st in "$@"; do
         tail -3 $out/smoke.log;;
     bench=*)   # bench=ARGS (comma-separated): one bench line with these arguments
         a=${st#bench=}; tagf=$(echo "$a" | tr -c 'A-Za-z0-9.' '_')
-        timeout -k 10 400 python -u bench.py ${a//,/ } > $out/bench_$tagf.json 2> $out/bench_$tagf.err
+        timeout -k 10 400 python -u bench.py --full ${a//,/ } > $out/bench_$tagf.json 2> $out/bench_$tagf.err
         rc=$?; echo "STEP bench $a rc=$rc"; [ $rc -eq 0 ] || fail bench_$tagf $out/bench_$tagf.err $rc
         python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['ms_per_step'], d.get('graph_replay_ms_per_step'))" $out/bench_$tagf.json "$a";;
     bench_*)
         cfg=${st#bench_}
-        timeout -k 10 400 python -u bench.py $(cfgargs $cfg) $(benchargs $cfg) > $out/$st.json 2> $out/$st.err
+        timeout -k 10 400 python -u bench.py --full $(cfgargs $cfg) $(benchargs $cfg) > $out/$st.json 2> $out/$st.err
         rc=$?; echo "STEP $st rc=$rc"; [ $rc -eq 0 ] || fail $st $out/$st.err $rc
         tail -c 2500 $out/$st.json; echo;;
     trace_py=*)   # rocprofv3 --kernel-trace --stats of a probe: trace_py=SCRIPT[:ARGS]

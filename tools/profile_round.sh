@@ -5,7 +5,7 @@
 set -e
 TAG=${1:-r01}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-exact-compare"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-exact-compare"
 mkdir -p $OUT
 cd /tmp
 export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 """Per-step start offsets of a rocprofv3 kernel trace of bench.py: for every CoulForce step (from
 one k_flux_terms to the next k_assemble_energy end) its duration, whether the cluster list was
 rebuilt (k_cl_build > 5 us), the grid bin sort's duration and when the pair kernel and the spread
-started.  Steps first..last (1-based) only; bench.py's passes run warmup, breakdown, timed, ...
+started.  Steps first..last (1-based) only; bench.py --full's passes run warmup, breakdown, timed, ...
 
 usage: python tools/step_stats.py TRACE_DIR [first last]
 """

@@ -5,7 +5,7 @@ the device idle).  Used to find the fork / join latencies of the two-stream step
 
 usage: python tools/step_timeline.py TRACE_DIR [EVAL]
 EVAL: index of the evaluation (k_assemble_energy launch) to show, default -2 (the graph pass of the
-bench command); with `bench.py --steps 5 --warmup 2` evaluations 8..12 are the timed region
+bench command); with `bench.py --full --steps 5 --warmup 2` evaluations 8..12 are the timed region
 (1 initial + 2 warm-up + 5 breakdown before it).
 """
 import csv, sys, glob
