@@ -28,7 +28,9 @@ extern "C" {
 #endif
 
 #define CF_API_VERSION 4   /* 2: cf_params.one_4pi_eps0; 3: cf_options.handover, pair_list, variants, list_capacity;
-                              4: device index guards (cf_get_device_errors), cf_compute_openmm, octant list removed */
+                              4: device index guards (cf_get_device_errors), cf_compute_openmm, octant list removed;
+                              still 4 (purely additive): cf_compute_batch, cf_compute_batch_host,
+                              cf_set_batch_limit, cf_get_batch_stats */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -211,7 +213,10 @@ CF_EXPORT int cf_get_fallback_stats(const cf_handle* h, int64_t* half_list_fallb
  * copied to host-mapped memory at the end of the evaluation, and every later entry point of the
  * handle (cf_compute*, cf_synchronize, cf_get_charges / _dedq / _energy_terms; cf_compute_host in
  * the same call) then returns CF_ERR_STATE naming the guard.  Sticky: re-create the handle.
- * cf_get_device_errors synchronises the handle's streams and returns the bits (0 = none). */
+ * cf_get_device_errors synchronises the handle's streams and returns the bits (0 = none).
+ * The batched path (cf_compute_batch) adds no guard bits: every index it uses is topological,
+ * validated by cf_create, or derived from the launch's own grid against N and nconf.  A guard that
+ * is already set makes cf_compute_batch fail like every other entry point. */
 #define CF_GUARD_CELL_BOUNDS 1
 #define CF_GUARD_CLUSTER_TABLE 2
 #define CF_GUARD_LIST_ENTRY 4
@@ -302,6 +307,41 @@ CF_EXPORT int cf_set_overlap(cf_handle* h, int enable);
  * OpenMM Reference/CPU-platform adapter calls.  forces_host is ADDED to. */
 CF_EXPORT int cf_compute_host(cf_handle* h, const double* pos_host, const double* box9, int flags,
                               double* forces_host, double* energy_host);
+
+/*
+ * Batched evaluation: nconf conformations of the handle's system in one call -- what fitting a
+ * charge-flux model needs (charges, energies and forces of thousands of small gas-phase
+ * conformations).  Non-periodic handles on one rank only: a periodic handle gives CF_ERR_INVALID,
+ * world_size > 1 CF_ERR_STATE, as does a call between cf_compute_begin and _end.
+ *   pos_dev     [nconf][N][3] fp64 DEVICE, conformation-major
+ *   forces_dev  [nconf][N][3] fp64 DEVICE, ADDED to (as cf_compute); NULL or no CF_INCLUDE_FORCES: untouched
+ *   energy_dev  [nconf] fp64 DEVICE, OVERWRITTEN (0 without CF_INCLUDE_ENERGY); NULL: not written
+ *   charges_dev [nconf][N] fp64 DEVICE, OVERWRITTEN with the charges after flux; NULL: not written
+ * Per conformation the result is cf_compute's on a non-periodic handle: the same flux formulas, the
+ * all-pairs sum with excluded pairs skipped, the chain rule, one_4pi_eps0; always fp64.  nconf = 0
+ * is a no-op.  A pass is at most four kernel launches whatever nconf (each kernel's grid spans
+ * conformations x atom tiles); every sum is taken in an order fixed by the system alone, so a
+ * conformation's results are bitwise reproducible and independent of what else is in the batch,
+ * of nconf and of the pass size.
+ * Asynchronous on the handle's stream: inputs and outputs must stay valid until the stream reaches
+ * them.  The first call, and any call that needs a larger workspace, allocates it and so
+ * synchronises the handle's streams.  The batch path has its own workspace: cf_get_charges /
+ * _dedq / _energy_terms / _neighbor_stats / _graph_stats keep reporting the last cf_compute, and
+ * the next cf_compute is unaffected.  Batch launches are always eager (never captured or replayed;
+ * the handle's graph mode stays as it was) and are not recorded by cf_set_timing.
+ * cf_update_parameters takes effect on the next batch call (the same parameter buffers are read).
+ */
+CF_EXPORT int cf_compute_batch(cf_handle* h, int32_t nconf, const double* pos_dev, int flags,
+                               double* forces_dev, double* energy_dev, double* charges_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H); forces_host ADDED to */
+CF_EXPORT int cf_compute_batch_host(cf_handle* h, int32_t nconf, const double* pos_host, int flags,
+                                    double* forces_host, double* energy_host, double* charges_host);
+/* cap on the conformations evaluated per pass (bounds the batch workspace); 0 = automatic: as many
+ * as keep the workspace (per conformation q[N], the flux slots, dq/dx, dE/dq[N], F[3N], e[N]) at
+ * or below 256 MiB, and never more than 65535.  A larger batch runs as consecutive passes. */
+CF_EXPORT int cf_set_batch_limit(cf_handle* h, int32_t max_conformations);
+/* since cf_create: batch calls, conformations evaluated, passes (chunks) launched; any output may be NULL */
+CF_EXPORT int cf_get_batch_stats(const cf_handle* h, int64_t* calls, int64_t* conformations, int64_t* passes);
 
 /* Diagnostics of the last evaluation (synchronous, host outputs).
  *   charges [N]  realcharges after charge flux          (ReferenceCoulKernels.cpp:37-228)

@@ -57,6 +57,13 @@ struct cf_handle {
     std::vector<int4> topo_terms;
     std::vector<int> topo_ex_start, topo_ex_list;
     GraphCache* graph = nullptr;   // cf_set_graph (owned; freed by graph_forget)
+    // cf_compute_batch: its own workspace (the single-evaluation buffers above are not touched),
+    // grown on demand up to the pass limit; both in H->allocs, so cf_destroy frees them
+    cf::BatchWs batch;
+    int batch_limit = 0;              // cf_set_batch_limit (0: automatic, kBatchAutoBytes)
+    int64_t batch_calls = 0, batch_confs = 0, batch_passes = 0;
+    double* batch_stage = nullptr;    // cf_compute_batch_host staging: pos, forces, charges, energies
+    int64_t batch_stage_confs = 0;
 };
 
 namespace {
@@ -1758,6 +1765,116 @@ CF_EXPORT int cf_compute_host(cf_handle* H, const double* pos_host, const double
             for (size_t k = 0; k < 3 * (size_t)n; k++) forces_host[k] += f[k];
         if (energy_host) *energy_host = e;
     });
+}
+
+// ---- batched evaluation (non-periodic, one rank; cf_kernels_batch.hip) -----------
+// The automatic pass size keeps the batch workspace at or below this many bytes
+constexpr size_t kBatchAutoBytes = (size_t)256 << 20;
+
+static int batch_pass_size(const cf_handle* H, int nconf) {
+    const size_t per = cf::batch_doubles_per_conf(H->h) * sizeof(double);
+    int64_t lim = H->batch_limit > 0 ? H->batch_limit : (int64_t)std::max<size_t>(1, kBatchAutoBytes / per);
+    lim = std::min<int64_t>(lim, cf::kBatchMaxPass);
+    return (int)std::min<int64_t>(lim, nconf);
+}
+
+CF_EXPORT int cf_compute_batch(cf_handle* H, int32_t nconf, const double* pos_dev, int flags, double* forces_dev,
+                               double* energy_dev, double* charges_dev) {
+    return guarded([&] {
+        if (!H || !pos_dev) fail(CF_ERR_INVALID, "null argument");
+        if (nconf < 0) fail(CF_ERR_INVALID, "nconf must be >= 0");
+        cf::Handle& h = H->h;
+        if (h.world > 1) fail(CF_ERR_STATE, "cf_compute_batch is single-rank only");
+        if (h.pbc) fail(CF_ERR_INVALID, "cf_compute_batch: batches are non-periodic only (this handle is periodic)");
+        if (h.pending_flags >= 0) fail(CF_ERR_STATE, "cf_compute_batch during a begun evaluation");
+        guard_check(h);
+        if (nconf == 0) return;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const int pass = batch_pass_size(H, nconf);
+        if (pass > H->batch.cap) {   // first call or growth: allocates (and so synchronises)
+            double* old = H->batch.base;
+            H->batch = cf::BatchWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_carve(h, base, pass, H->batch);
+        }
+        // eager launches on the handle's stream, never captured or replayed (graph mode is left as
+        // it is) and not bracketed by the per-phase timing events
+        const size_t n = (size_t)h.n;
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            cf::launch_batch(h, H->batch, m, pos_dev + 3 * n * c0, flags, forces_dev ? forces_dev + 3 * n * c0 : nullptr,
+                             energy_dev ? energy_dev + c0 : nullptr, charges_dev ? charges_dev + n * c0 : nullptr);
+            H->batch_passes++;
+        }
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        launch_check(h, "compute_batch");
+    });
+}
+
+CF_EXPORT int cf_compute_batch_host(cf_handle* H, int32_t nconf, const double* pos_host, int flags,
+                                    double* forces_host, double* energy_host, double* charges_host) {
+    return guarded([&] {
+        if (!H || !pos_host) fail(CF_ERR_INVALID, "null argument");
+        if (nconf < 0) fail(CF_ERR_INVALID, "nconf must be >= 0");
+        cf::Handle& h = H->h;
+        if (h.world > 1) fail(CF_ERR_STATE, "cf_compute_batch_host is single-rank only");
+        if (h.pbc) fail(CF_ERR_INVALID, "cf_compute_batch_host: batches are non-periodic only (this handle is periodic)");
+        if (nconf == 0) {
+            if (h.pending_flags >= 0) fail(CF_ERR_STATE, "cf_compute_batch_host during a begun evaluation");
+            guard_check(h);
+            return;
+        }
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, B = (size_t)nconf;
+        if (nconf > H->batch_stage_confs) {
+            double* old = H->batch_stage;
+            H->batch_stage = nullptr; H->batch_stage_confs = 0;
+            dfree(H, old);
+            H->batch_stage = dalloc<double>(H, B * (3 * n + 3 * n + n + 1));
+            H->batch_stage_confs = nconf;
+        }
+        double* pos = H->batch_stage;
+        double* frc = pos + 3 * n * B;
+        double* chg = frc + 3 * n * B;
+        double* ene = chg + n * B;
+        const bool fw = forces_host && (flags & CF_INCLUDE_FORCES);
+        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D positions");
+        if (fw) check_hip(hipMemsetAsync(frc, 0, sizeof(double) * 3 * n * B, h.stream), "memset forces");
+        const int rc = cf_compute_batch(H, nconf, pos, flags, fw ? frc : nullptr, energy_host ? ene : nullptr,
+                                        charges_host ? chg : nullptr);
+        if (rc != CF_OK) throw CfError(rc, g_err);
+        std::vector<double> f(fw ? 3 * n * B : 0);
+        if (fw)
+            check_hip(hipMemcpyAsync(f.data(), frc, sizeof(double) * 3 * n * B, hipMemcpyDeviceToHost, h.stream),
+                      "D2H forces");
+        if (energy_host)
+            check_hip(hipMemcpyAsync(energy_host, ene, sizeof(double) * B, hipMemcpyDeviceToHost, h.stream), "D2H energies");
+        if (charges_host)
+            check_hip(hipMemcpyAsync(charges_host, chg, sizeof(double) * n * B, hipMemcpyDeviceToHost, h.stream),
+                      "D2H charges");
+        check_hip(hipStreamSynchronize(h.stream), "sync");
+        if (fw)
+            for (size_t k = 0; k < f.size(); k++) forces_host[k] += f[k];
+    });
+}
+
+CF_EXPORT int cf_set_batch_limit(cf_handle* H, int32_t max_conformations) {
+    return guarded([&] {
+        if (!H) fail(CF_ERR_INVALID, "null handle");
+        if (max_conformations < 0) fail(CF_ERR_INVALID, "max_conformations must be >= 0 (0 = automatic)");
+        H->batch_limit = max_conformations;
+    });
+}
+
+CF_EXPORT int cf_get_batch_stats(const cf_handle* H, int64_t* calls, int64_t* conformations, int64_t* passes) {
+    if (!H) { g_err = "null handle"; return CF_ERR_INVALID; }
+    if (calls) *calls = H->batch_calls;
+    if (conformations) *conformations = H->batch_confs;
+    if (passes) *passes = H->batch_passes;
+    return CF_OK;
 }
 
 CF_EXPORT int cf_get_charges(cf_handle* H, double* out) {

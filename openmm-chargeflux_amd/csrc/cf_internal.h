@@ -316,6 +316,25 @@ void launch_om_gather(Handle& h, const void* posq, const void* corr, int posq_ki
 void launch_om_scatter(Handle& h, const int* atom_index, const double* frc, int padded, long long* fbuf,
                        const double* ene, void* ebuf, int energy_kind);
 
+// batched non-periodic evaluation (cf_kernels_batch.hip, cf_compute_batch): the workspace of one
+// pass, conformation-major arrays carved from one allocation of cap * batch_doubles_per_conf doubles
+struct BatchWs {
+    double* base = nullptr;
+    int cap = 0;                // conformations the arrays hold
+    double* q = nullptr;        // [cap][N] charges after flux
+    double* dq_slot = nullptr;  // [cap][S]
+    double* dqdx = nullptr;     // [cap][D*3]
+    double* dedq = nullptr;     // [cap][N]
+    double* f_part = nullptr;   // [cap][N*3]
+    double* e_atom = nullptr;   // [cap][N] per-atom pair energies
+};
+constexpr int kBatchMaxPass = 65535;   // conformations per pass: gridDim.y
+size_t batch_doubles_per_conf(const Handle& h);
+void batch_carve(const Handle& h, double* base, int cap, BatchWs& w);
+// one pass of nconf <= w.cap conformations on h.stream: at most four launches, whatever nconf
+void launch_batch(Handle& h, const BatchWs& w, int nconf, const double* pos, int flags, double* forces,
+                  double* energy, double* charges);
+
 void check_hip(hipError_t e, const char* what);
 
 // ---- fp64 math helpers shared by the pair and grid kernels -------------------------

@@ -271,6 +271,71 @@ class HipCalcCoulForceKernel:
                                                 int(padded_n), _dp(b9), self._flags(includeForces, includeEnergy),
                                                 ptr(force_buffer), ptr(energy_buffer), ekind), self._lib)
 
+    # batched evaluation (cf_compute_batch: non-periodic systems, one rank) ------------------
+    def _check_batch_array(self, a, name, trailing, module=np):
+        """(B,) + trailing, float64, C-contiguous -- checked before the C call."""
+        shape = tuple(a.shape)
+        if len(shape) != 1 + len(trailing) or shape[1:] != trailing:
+            raise ValueError(f"{name} must have shape (B,) + {trailing}, got {shape}")
+        if module is np:
+            ok = a.dtype == np.float64 and a.flags.c_contiguous
+        else:
+            ok = a.dtype == module.float64 and a.is_contiguous()
+        if not ok:
+            raise ValueError(f"{name} must be a C-contiguous float64 array")
+        return shape[0]
+
+    def execute_batch_host(self, positions, includeForces=True, includeEnergy=True, forces=None,
+                           return_charges=True):
+        """B conformations of the system in one call (cf_compute_batch_host): positions (B,N,3)
+        float64 C-contiguous numpy array; forces (B,N,3) ADDED to (created if None).  Returns
+        (energies (B,), forces (B,N,3), charges (B,N) after flux, or None)."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        if forces is None:
+            forces = np.zeros((nconf, self._n, 3))
+        elif not isinstance(forces, np.ndarray) or self._check_batch_array(forces, "forces", (self._n, 3)) != nconf:
+            raise ValueError("forces must be a float64 numpy array shaped like positions")
+        energies = np.zeros(nconf)
+        charges = np.zeros((nconf, self._n)) if return_charges else None
+        _cabi.check(self._lib.cf_compute_batch_host(self._h, nconf, _dp(positions),
+                                                    self._flags(includeForces, includeEnergy), _dp(forces),
+                                                    _dp(energies), _dp(charges) if return_charges else None),
+                    self._lib)
+        return energies, forces, charges
+
+    def execute_batch_device(self, positions, includeForces, includeEnergy, forces=None, energies=None,
+                             charges=None):
+        """The same on torch tensors (float64, on the kernel's device, contiguous): positions
+        (B,N,3); forces (B,N,3) ADDED to, energies (B,) and charges (B,N) overwritten; each output
+        may be None.  Asynchronous on the kernel's stream."""
+        import torch
+        if not isinstance(positions, torch.Tensor):
+            raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
+        for t, name, trailing in ((forces, "forces", (self._n, 3)), (energies, "energies", ()),
+                                  (charges, "charges", (self._n,))):
+            if t is not None and (not isinstance(t, torch.Tensor)
+                                  or self._check_batch_array(t, name, trailing, torch) != nconf):
+                raise ValueError(f"{name} must be a float64 torch tensor for {nconf} conformations")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _cabi.check(self._lib.cf_compute_batch(self._h, nconf, ptr(positions),
+                                               self._flags(includeForces, includeEnergy), ptr(forces),
+                                               ptr(energies), ptr(charges)), self._lib)
+
+    def set_batch_limit(self, n: int):
+        """Conformations evaluated per pass of a batch (bounds the batch workspace); 0 = automatic
+        (a 256 MiB workspace).  Results do not depend on it."""
+        _cabi.check(self._lib.cf_set_batch_limit(self._h, int(n)), self._lib)
+        return self
+
+    def batch_stats(self):
+        """(batch calls, conformations evaluated, passes launched) since initialize."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _cabi.check(self._lib.cf_get_batch_stats(self._h, C.byref(a), C.byref(b), C.byref(c)), self._lib)
+        return a.value, b.value, c.value
+
     def device_errors(self):
         """CF_GUARD_* bits of the device index guards tripped so far (0 = none; synchronises)."""
         v = C.c_int32()
