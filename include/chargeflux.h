@@ -30,7 +30,8 @@ extern "C" {
 #define CF_API_VERSION 4   /* 2: cf_params.one_4pi_eps0; 3: cf_options.handover, pair_list, variants, list_capacity;
                               4: device index guards (cf_get_device_errors), cf_compute_openmm, octant list removed;
                               still 4 (purely additive): cf_compute_batch, cf_compute_batch_host,
-                              cf_set_batch_limit, cf_get_batch_stats */
+                              cf_set_batch_limit, cf_get_batch_stats; cf_compute_batch_periodic,
+                              cf_compute_batch_periodic_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -336,9 +337,49 @@ CF_EXPORT int cf_compute_batch(cf_handle* h, int32_t nconf, const double* pos_de
 /* synchronous host-memory form of the same (H2D, evaluate, D2H); forces_host ADDED to */
 CF_EXPORT int cf_compute_batch_host(cf_handle* h, int32_t nconf, const double* pos_host, int flags,
                                     double* forces_host, double* energy_host, double* charges_host);
+/*
+ * The same for a PERIODIC handle, one box per conformation -- condensed-phase training frames
+ * (small boxes from NVT / NPT trajectories).  Arrays as cf_compute_batch, plus
+ *   boxes_host  [nconf][9] fp64 HOST, box vectors a, b, c per conformation as cf_compute's box9
+ *               (OpenMM's reduced form, orthorhombic or triclinic; a batch may mix both)
+ * boxes_host is read during the call (copied to a pinned buffer of the handle and uploaded from
+ * there): the caller may free or overwrite it as soon as the call returns.  Reusing the pinned
+ * buffer makes a call wait until the box upload of the previous periodic batch call on this handle
+ * has finished (that upload precedes the previous call's kernels on the stream; no other
+ * synchronisation in steady state).
+ * Every box is checked on the host by cf_compute's rules (reduced form, lengths > 0, cutoff <= half
+ * of each diagonal length), all of them before anything is launched: a bad box gives CF_ERR_INVALID
+ * with a message naming the conformation index, no output touched, no statistic counted.
+ * Per conformation the result is cf_compute's on this handle with that box and kspace_algo 0: flux
+ * charges with the box-vector minimum image, the self term, the exact reciprocal sum over the
+ * reference's half-space k set (box diagonals), real space over every pair once by minimum image
+ * within the cutoff with excluded pairs left out, the erf correction of every excluded pair (any
+ * distance), the chain rule.  alpha and kmax are cf_create's (from the default box) whatever the
+ * conformation's box, as in cf_compute.  The energy follows cf_compute's flags on a periodic
+ * handle, the reference's quirk included: self, direct and exclusion energy are accumulated
+ * without CF_INCLUDE_ENERGY, the reciprocal part only with it.  Always fp64 and the exact k-sum,
+ * all pairs without a cell or neighbour list: the handle's kspace_algo, grid_width, precision,
+ * pair_list, skin and graph mode are ignored and left as they are.
+ * A non-periodic handle gives CF_ERR_INVALID, world_size > 1 and a call between cf_compute_begin
+ * and _end CF_ERR_STATE, NULL pos or boxes and nconf < 0 CF_ERR_INVALID; nconf = 0 is a no-op.  A
+ * pass is at most seven kernel launches whatever nconf; every sum's order depends only on N, the
+ * topology and kmax, so a conformation's results are bitwise the same alone, at any position of
+ * any batch and under any pass size.  Asynchrony, the lazily grown workspace of its own (growth
+ * allocates and synchronises; cf_destroy frees it), isolation from cf_compute and its diagnostics,
+ * eager launches outside cf_set_timing, cf_update_parameters: as cf_compute_batch.  No guard bits.
+ */
+CF_EXPORT int cf_compute_batch_periodic(cf_handle* h, int32_t nconf, const double* pos_dev,
+                                        const double* boxes_host, int flags, double* forces_dev,
+                                        double* energy_dev, double* charges_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H); forces_host ADDED to */
+CF_EXPORT int cf_compute_batch_periodic_host(cf_handle* h, int32_t nconf, const double* pos_host,
+                                             const double* boxes_host, int flags, double* forces_host,
+                                             double* energy_host, double* charges_host);
 /* cap on the conformations evaluated per pass (bounds the batch workspace); 0 = automatic: as many
- * as keep the workspace (per conformation q[N], the flux slots, dq/dx, dE/dq[N], F[3N], e[N]) at
- * or below 256 MiB, and never more than 65535.  A larger batch runs as consecutive passes. */
+ * as keep the workspace (per conformation q[N], the flux slots, dq/dx, dE/dq[N], F[3N], e[N]; a
+ * periodic batch also the phase tables, 4 doubles per [N][kmax_x + kmax_y + kmax_z] entry, and 3
+ * doubles per k-vector) at or below 256 MiB, and never more than 65535.  A larger batch runs as consecutive
+ * passes.  Applies to both batch forms; cf_get_batch_stats counts both. */
 CF_EXPORT int cf_set_batch_limit(cf_handle* h, int32_t max_conformations);
 /* since cf_create: batch calls, conformations evaluated, passes (chunks) launched; any output may be NULL */
 CF_EXPORT int cf_get_batch_stats(const cf_handle* h, int64_t* calls, int64_t* conformations, int64_t* passes);

@@ -64,6 +64,15 @@ struct cf_handle {
     int64_t batch_calls = 0, batch_confs = 0, batch_passes = 0;
     double* batch_stage = nullptr;    // cf_compute_batch_host staging: pos, forces, charges, energies
     int64_t batch_stage_confs = 0;
+    // cf_compute_batch_periodic: its workspace (in H->allocs) and the boxes of the call in flight:
+    // a pinned host copy (so the caller's array is free when the call returns) uploaded to
+    // batch_boxes_dev; batch_boxes_ev marks the upload's end (the next call waits for it before it
+    // overwrites the pinned copy)
+    cf::BatchPbcWs batch_pbc;
+    double* batch_boxes_pin = nullptr;   // [batch_boxes_cap][8] pinned host
+    double* batch_boxes_dev = nullptr;   // [batch_boxes_cap][8] device (in H->allocs)
+    int64_t batch_boxes_cap = 0;
+    hipEvent_t batch_boxes_ev = nullptr;
 };
 
 namespace {
@@ -829,6 +838,8 @@ CF_EXPORT int cf_destroy(cf_handle* H) {
         if (H->h.ev_fork) (void)hipEventDestroy(H->h.ev_fork);
         if (H->h.ev_join) (void)hipEventDestroy(H->h.ev_join);
         if (H->h.err_host) (void)hipHostFree(H->h.err_host);
+        if (H->batch_boxes_pin) (void)hipHostFree(H->batch_boxes_pin);
+        if (H->batch_boxes_ev) (void)hipEventDestroy(H->batch_boxes_ev);
         delete H;
     });
 }
@@ -1845,6 +1856,133 @@ CF_EXPORT int cf_compute_batch_host(cf_handle* H, int32_t nconf, const double* p
         if (fw) check_hip(hipMemsetAsync(frc, 0, sizeof(double) * 3 * n * B, h.stream), "memset forces");
         const int rc = cf_compute_batch(H, nconf, pos, flags, fw ? frc : nullptr, energy_host ? ene : nullptr,
                                         charges_host ? chg : nullptr);
+        if (rc != CF_OK) throw CfError(rc, g_err);
+        std::vector<double> f(fw ? 3 * n * B : 0);
+        if (fw)
+            check_hip(hipMemcpyAsync(f.data(), frc, sizeof(double) * 3 * n * B, hipMemcpyDeviceToHost, h.stream),
+                      "D2H forces");
+        if (energy_host)
+            check_hip(hipMemcpyAsync(energy_host, ene, sizeof(double) * B, hipMemcpyDeviceToHost, h.stream), "D2H energies");
+        if (charges_host)
+            check_hip(hipMemcpyAsync(charges_host, chg, sizeof(double) * n * B, hipMemcpyDeviceToHost, h.stream),
+                      "D2H charges");
+        check_hip(hipStreamSynchronize(h.stream), "sync");
+        if (fw)
+            for (size_t k = 0; k < f.size(); k++) forces_host[k] += f[k];
+    });
+}
+
+// ---- batched periodic evaluation (one box per conformation; cf_kernels_batch_pbc.hip) -------------
+// Everything that can refuse the call, before anything is launched, staged or counted.
+static void batch_periodic_precheck(cf_handle* H, int32_t nconf, const double* pos, const double* boxes_host,
+                                    const char* name) {
+    if (!H || !pos || !boxes_host) fail(CF_ERR_INVALID, "null argument");
+    if (nconf < 0) fail(CF_ERR_INVALID, "nconf must be >= 0");
+    cf::Handle& h = H->h;
+    if (h.world > 1) fail(CF_ERR_STATE, std::string(name) + " is single-rank only");
+    if (!h.pbc) fail(CF_ERR_INVALID, std::string(name) + ": this handle is not periodic (use cf_compute_batch)");
+    if (h.pending_flags >= 0) fail(CF_ERR_STATE, std::string(name) + " during a begun evaluation");
+    guard_check(h);
+    // every box by the rules of set_box, all of them before the first launch
+    for (int32_t c = 0; c < nconf; c++) {
+        const double* b = boxes_host + 9 * (size_t)c;
+        const std::string what = std::string(name) + ": box of conformation " + std::to_string(c);
+        check_box_reduced(b, what.c_str());
+        const double L[3] = {b[0], b[4], b[8]};
+        for (int d = 0; d < 3; d++)
+            if (h.cutoff > 0.5 * L[d] * (1 + 1e-12))
+                fail(CF_ERR_INVALID, what + ": cutoff exceeds half the periodic box (minimum image would be ambiguous)");
+    }
+}
+
+static int batch_pbc_pass_size(const cf_handle* H, int nconf) {
+    const size_t per = cf::batch_pbc_doubles_per_conf(H->h) * sizeof(double);
+    int64_t lim = H->batch_limit > 0 ? H->batch_limit : (int64_t)std::max<size_t>(1, kBatchAutoBytes / per);
+    lim = std::min<int64_t>(lim, cf::kBatchMaxPass);
+    return (int)std::min<int64_t>(lim, nconf);
+}
+
+CF_EXPORT int cf_compute_batch_periodic(cf_handle* H, int32_t nconf, const double* pos_dev, const double* boxes_host,
+                                        int flags, double* forces_dev, double* energy_dev, double* charges_dev) {
+    return guarded([&] {
+        batch_periodic_precheck(H, nconf, pos_dev, boxes_host, "cf_compute_batch_periodic");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const int pass = batch_pbc_pass_size(H, nconf);
+        if (pass > H->batch_pbc.cap) {   // first call or growth: allocates (and so synchronises)
+            double* old = H->batch_pbc.base;
+            H->batch_pbc = cf::BatchPbcWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_pbc_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_pbc_carve(h, base, pass, H->batch_pbc);
+        }
+        // the boxes: (Lx, Ly, Lz, bx, cx, cy, 0, 0) per conformation into the pinned copy, one upload
+        // for the whole call.  The pinned copy of the previous call is reused once its upload is done
+        // (a wait for that copy, which the stream reached before the previous call's kernels).
+        if (!H->batch_boxes_ev) check_hip(hipEventCreateWithFlags(&H->batch_boxes_ev, hipEventDisableTiming), "hipEventCreate");
+        else check_hip(hipEventSynchronize(H->batch_boxes_ev), "hipEventSynchronize (boxes)");
+        if (nconf > H->batch_boxes_cap) {
+            if (H->batch_boxes_pin) (void)hipHostFree(H->batch_boxes_pin);
+            H->batch_boxes_pin = nullptr;
+            double* old = H->batch_boxes_dev;
+            H->batch_boxes_dev = nullptr; H->batch_boxes_cap = 0;
+            dfree(H, old);
+            check_hip(hipHostMalloc((void**)&H->batch_boxes_pin, sizeof(double) * 8 * (size_t)nconf, hipHostMallocDefault),
+                      "hipHostMalloc (boxes)");
+            H->batch_boxes_dev = dalloc<double>(H, 8 * (size_t)nconf);
+            H->batch_boxes_cap = nconf;
+        }
+        for (int32_t c = 0; c < nconf; c++) {
+            const double* b = boxes_host + 9 * (size_t)c;
+            double* o = H->batch_boxes_pin + 8 * (size_t)c;
+            o[0] = b[0]; o[1] = b[4]; o[2] = b[8]; o[3] = b[3]; o[4] = b[6]; o[5] = b[7]; o[6] = 0; o[7] = 0;
+        }
+        check_hip(hipMemcpyAsync(H->batch_boxes_dev, H->batch_boxes_pin, sizeof(double) * 8 * (size_t)nconf,
+                                 hipMemcpyHostToDevice, h.stream), "H2D boxes");
+        check_hip(hipEventRecord(H->batch_boxes_ev, h.stream), "hipEventRecord (boxes)");
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events; the handle's k-space algorithm, precision, list and skin are not used
+        const size_t n = (size_t)h.n;
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            cf::launch_batch_pbc(h, H->batch_pbc, m, pos_dev + 3 * n * c0, H->batch_boxes_dev + 8 * (size_t)c0, flags,
+                                 forces_dev ? forces_dev + 3 * n * c0 : nullptr, energy_dev ? energy_dev + c0 : nullptr,
+                                 charges_dev ? charges_dev + n * c0 : nullptr);
+            H->batch_passes++;
+        }
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        launch_check(h, "compute_batch_periodic");
+    });
+}
+
+CF_EXPORT int cf_compute_batch_periodic_host(cf_handle* H, int32_t nconf, const double* pos_host,
+                                             const double* boxes_host, int flags, double* forces_host,
+                                             double* energy_host, double* charges_host) {
+    return guarded([&] {
+        batch_periodic_precheck(H, nconf, pos_host, boxes_host, "cf_compute_batch_periodic_host");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, B = (size_t)nconf;
+        if (nconf > H->batch_stage_confs) {
+            double* old = H->batch_stage;
+            H->batch_stage = nullptr; H->batch_stage_confs = 0;
+            dfree(H, old);
+            H->batch_stage = dalloc<double>(H, B * (3 * n + 3 * n + n + 1));
+            H->batch_stage_confs = nconf;
+        }
+        double* pos = H->batch_stage;
+        double* frc = pos + 3 * n * B;
+        double* chg = frc + 3 * n * B;
+        double* ene = chg + n * B;
+        const bool fw = forces_host && (flags & CF_INCLUDE_FORCES);
+        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D positions");
+        if (fw) check_hip(hipMemsetAsync(frc, 0, sizeof(double) * 3 * n * B, h.stream), "memset forces");
+        const int rc = cf_compute_batch_periodic(H, nconf, pos, boxes_host, flags, fw ? frc : nullptr,
+                                                 energy_host ? ene : nullptr, charges_host ? chg : nullptr);
         if (rc != CF_OK) throw CfError(rc, g_err);
         std::vector<double> f(fw ? 3 * n * B : 0);
         if (fw)

@@ -1,5 +1,6 @@
 // cf_flux.h -- the charge-flux term bodies, shared by the single-evaluation kernel k_flux_terms
-// (cf_kernels_core.hip) and the batched one k_b_flux (cf_kernels_batch.hip): one definition of the
+// (cf_kernels_core.hip) and the batched ones k_b_flux (cf_kernels_batch.hip) and k_bp_flux
+// (cf_kernels_batch_pbc.hip), with the other bodies the batched kernels share: one definition of the
 // reference's formulas (ReferenceCoulKernels.cpp, RCK: bonds :42-80, angles :81-162, waters
 // :163-227), so the two paths cannot drift apart.
 #pragma once
@@ -86,6 +87,80 @@ __device__ __forceinline__ void flux_term(int t, int4 ti, const double* __restri
             o[24 + j] = a13k1 + ub;
         }
     }
+}
+
+// ---- bodies shared by the batched kernels (cf_kernels_batch.hip, cf_kernels_batch_pbc.hip) -------
+// The (conformation, term) pairs of a batch are flattened, g = c * nterms + t; dq/dx is
+// [conformation][D * 3], so a block's output is one contiguous run across conformations.
+__device__ __forceinline__ long batch_dqdx_at(long g, int nterms, int nb, int na, long nd3) {
+    return (g / nterms) * nd3 + dqdx_start((int)(g % nterms), nb, na);
+}
+
+// one block of 256 flattened (conformation, term) pairs: the lane's term into st (LDS, 256 * 27
+// doubles), then the block's dq/dx run written coalesced.  PBC: the conformation's box from boxes
+// ([conformation][8]: Lx, Ly, Lz, bx, cx, cy, -, -), box-vector minimum image; else no box.
+template <bool PBC>
+__device__ __forceinline__ void batch_flux_block(int nconf, int n, int nterms, int nb, int na, int nslots, long nd3,
+                                                 const int4* __restrict__ tidx, const double* __restrict__ tpar,
+                                                 const double* __restrict__ pos_all, const double* __restrict__ boxes,
+                                                 int pbc, double* __restrict__ dq_slot_all,
+                                                 double* __restrict__ dqdx_all, double* st) {
+    const long total = (long)nconf * nterms;
+    const long g0 = (long)blockIdx.x * 256;
+    const long g = g0 + threadIdx.x;
+    const long base = batch_dqdx_at(g0, nterms, nb, na, nd3);
+    if (g < total) {
+        const size_t c = (size_t)(g / nterms);
+        const int t = (int)(g % nterms);
+        double3 L = make_double3(0.0, 0.0, 0.0), T = make_double3(0.0, 0.0, 0.0);
+        if (PBC) {
+            const double* b = boxes + 8 * c;
+            L = make_double3(b[0], b[1], b[2]);
+            T = make_double3(b[3], b[4], b[5]);
+        }
+        flux_term(t, tidx[t], tpar + 5 * t, nb, na, pos_all + c * 3 * (size_t)n, L, T, PBC ? pbc : 0,
+                  dq_slot_all + c * (size_t)nslots, st + (batch_dqdx_at(g, nterms, nb, na, nd3) - base));
+    }
+    __syncthreads();
+    const int len = (int)(batch_dqdx_at(min(g0 + 256, total), nterms, nb, na, nd3) - base);
+    for (int e = threadIdx.x; e < len; e += 256) dqdx_all[base + e] = st[e];
+}
+
+// chain rule of atom b: (fx, fy, fz) -= sum_e dE/dq[a_e] dq_{a_e}/dx_b over the ccsr entries of b
+// in entry order (k_assemble_energy's gather), batches of 4 entries in flight
+__device__ __forceinline__ void chain_rule_atom(int b, const int* __restrict__ cs, const int2* __restrict__ ce,
+                                                const double* __restrict__ dedq, const double* __restrict__ dqdx,
+                                                double& fx, double& fy, double& fz) {
+    const int k1 = cs[b + 1];
+    for (int k0 = cs[b]; k0 < k1; k0 += 4) {   // batches of 4 entries in flight, summed in entry order
+        int2 en[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) en[u] = ce[min(k0 + u, k1 - 1)];
+        double g[4], d[4][3];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            g[u] = dedq[en[u].y];
+            d[u][0] = dqdx[3 * en[u].x]; d[u][1] = dqdx[3 * en[u].x + 1]; d[u][2] = dqdx[3 * en[u].x + 2];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            if (k0 + u < k1) {
+                fx -= g[u] * d[u][0];
+                fy -= g[u] * d[u][1];
+                fz -= g[u] * d[u][2];
+            }
+        }
+    }
+}
+
+// sum of a over the 256 threads of a block, in a fixed order: a butterfly within each wave, then
+// the four waves as (w0 + w1) + (w2 + w3), stored to *out by thread 0.  red: 4 doubles of LDS.
+__device__ __forceinline__ void block_sum_256_store(double a, double* red, double* out) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) a += __shfl_xor(a, m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // true if j is one of the cnt exclusion partners ex_list[ex0, ex0 + cnt), the first kMaxRegExcl of

@@ -335,6 +335,32 @@ void batch_carve(const Handle& h, double* base, int cap, BatchWs& w);
 void launch_batch(Handle& h, const BatchWs& w, int nconf, const double* pos, int flags, double* forces,
                   double* energy, double* charges);
 
+void launch_batch_charges(Handle& h, int nconf, const double* dq_slot, double* q, double* charges);   // k_b_charges
+
+// batched periodic evaluation (cf_kernels_batch_pbc.hip, cf_compute_batch_periodic): one box per
+// conformation, all pairs by minimum image + the exact k-sum.  Workspace of one pass, carved from
+// one allocation of cap * batch_pbc_doubles_per_conf doubles (the double2 arrays first: 16-B aligned)
+struct BatchPbcWs {
+    double* base = nullptr;
+    int cap = 0;                // conformations the arrays hold
+    double2* tab = nullptr;     // [cap][N][KX + KY + KZ] per-axis phases e^{i m (2 pi / L_a) x_a}
+    double2* tab_t = nullptr;   // [cap][KX + KY + KZ][N] the same, entry-major (lanes = atoms read it coalesced)
+    double2* coef = nullptr;    // [cap][khalf] 2 c eak (Re S, Im S)
+    double* ek = nullptr;       // [cap][khalf] c eak |S|^2
+    double* q = nullptr;        // [cap][N] charges after flux
+    double* dq_slot = nullptr;  // [cap][S]
+    double* dqdx = nullptr;     // [cap][D*3]
+    double* dedq = nullptr;     // [cap][N]
+    double* f_part = nullptr;   // [cap][N*3]
+    double* e_atom = nullptr;   // [cap][N] self + direct + exclusion energy per atom
+};
+size_t batch_pbc_doubles_per_conf(const Handle& h);
+void batch_pbc_carve(const Handle& h, double* base, int cap, BatchPbcWs& w);
+// one pass of nconf <= w.cap conformations on h.stream: at most seven launches, whatever nconf.
+// boxes: device, [nconf][8] = (Lx, Ly, Lz, bx, cx, cy, -, -) per conformation
+void launch_batch_pbc(Handle& h, const BatchPbcWs& w, int nconf, const double* pos, const double* boxes, int flags,
+                      double* forces, double* energy, double* charges);
+
 void check_hip(hipError_t e, const char* what);
 
 // ---- fp64 math helpers shared by the pair and grid kernels -------------------------

@@ -28,29 +28,13 @@ namespace cf {
 //    The (conformation, term) pairs are flattened, g = c * nterms + t, so that a system with few
 //    terms still fills its blocks; dq/dx is [conformation][D * 3], and a conformation's terms end
 //    where the next one's begin, so a block's output is one contiguous run across conformations.
-__device__ __forceinline__ long batch_dqdx_at(long g, int nterms, int nb, int na, long nd3) {
-    return (g / nterms) * nd3 + dqdx_start((int)(g % nterms), nb, na);
-}
-
 __global__ void __launch_bounds__(256) k_b_flux(int nconf, int n, int nterms, int nb, int na, int nslots, long nd3,
                                                 const int4* __restrict__ tidx, const double* __restrict__ tpar,
                                                 const double* __restrict__ pos_all, double* __restrict__ dq_slot_all,
                                                 double* __restrict__ dqdx_all) {
     __shared__ double st[256 * 27];
-    const long total = (long)nconf * nterms;
-    const long g0 = (long)blockIdx.x * 256;
-    const long g = g0 + threadIdx.x;
-    const long base = batch_dqdx_at(g0, nterms, nb, na, nd3);
-    const double3 zero = make_double3(0.0, 0.0, 0.0);
-    if (g < total) {
-        const size_t c = (size_t)(g / nterms);
-        const int t = (int)(g % nterms);
-        flux_term(t, tidx[t], tpar + 5 * t, nb, na, pos_all + c * 3 * (size_t)n, zero, zero, 0,
-                  dq_slot_all + c * (size_t)nslots, st + (batch_dqdx_at(g, nterms, nb, na, nd3) - base));
-    }
-    __syncthreads();
-    const int len = (int)(batch_dqdx_at(min(g0 + 256, total), nterms, nb, na, nd3) - base);
-    for (int e = threadIdx.x; e < len; e += 256) dqdx_all[base + e] = st[e];
+    batch_flux_block<false>(nconf, n, nterms, nb, na, nslots, nd3, tidx, tpar, pos_all, nullptr, 0, dq_slot_all,
+                            dqdx_all, st);
 }
 
 // ---------------------------------------------------------------------------------
@@ -170,26 +154,7 @@ __global__ void __launch_bounds__(256) k_b_assemble(int n, long nd3, const int* 
         const double* f_part = f_part_all + c * 3 * (size_t)n;
         double* out = out_all + c * 3 * (size_t)n;
         double fx = f_part[3 * b], fy = f_part[3 * b + 1], fz = f_part[3 * b + 2];
-        const int k1 = cs[b + 1];
-        for (int k0 = cs[b]; k0 < k1; k0 += 4) {   // batches of 4 entries in flight, summed in entry order
-            int2 en[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) en[u] = ce[min(k0 + u, k1 - 1)];
-            double g[4], d[4][3];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                g[u] = dedq[en[u].y];
-                d[u][0] = dqdx[3 * en[u].x]; d[u][1] = dqdx[3 * en[u].x + 1]; d[u][2] = dqdx[3 * en[u].x + 2];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                if (k0 + u < k1) {
-                    fx -= g[u] * d[u][0];
-                    fy -= g[u] * d[u][1];
-                    fz -= g[u] * d[u][2];
-                }
-            }
-        }
+        chain_rule_atom(b, cs, ce, dedq, dqdx, fx, fy, fz);
         out[3 * b] += fx;
         out[3 * b + 1] += fy;
         out[3 * b + 2] += fz;
@@ -200,11 +165,7 @@ __global__ void __launch_bounds__(256) k_b_assemble(int n, long nd3, const int* 
         const double* e_atom = e_atom_all + c * (size_t)n;
         for (int k = threadIdx.x; k < n; k += 256) a += e_atom[k];
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) a += __shfl_xor(a, m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) energy_out[c] = (red[0] + red[1]) + (red[2] + red[3]);
+    block_sum_256_store(a, red, energy_out + c);
 }
 
 // ---------------------------------------------------------------------------------
@@ -228,6 +189,12 @@ void batch_carve(const Handle& h, double* base, int cap, BatchWs& w) {
     w.e_atom = w.f_part + c * 3 * n;
 }
 
+// k_b_charges for nconf conformations (also the charges stage of the periodic batch)
+void launch_batch_charges(Handle& h, int nconf, const double* dq_slot, double* q, double* charges) {
+    hipLaunchKernelGGL(k_b_charges, dim3(nblk(h.n, 256), nconf), dim3(256), 0, h.stream, h.n, h.nslots_dq, h.q0,
+                       h.qcsr_start, h.qcsr_slot, dq_slot, q, charges);
+}
+
 void launch_batch(Handle& h, const BatchWs& w, int nconf, const double* pos, int flags, double* forces,
                   double* energy, double* charges) {
     if (nconf <= 0 || nconf > w.cap || nconf > kBatchMaxPass) throw std::invalid_argument("launch_batch: pass size");
@@ -238,8 +205,7 @@ void launch_batch(Handle& h, const BatchWs& w, int nconf, const double* pos, int
     if (h.nterms > 0)
         hipLaunchKernelGGL(k_b_flux, dim3(nblk((int64_t)nconf * h.nterms, 256)), dim3(256), 0, h.stream, nconf, n,
                            h.nterms, h.nb, h.na, h.nslots_dq, nd3, h.term_idx, h.term_par, pos, w.dq_slot, w.dqdx);
-    hipLaunchKernelGGL(k_b_charges, dim3(nblk(n, 256), nconf), dim3(256), 0, h.stream, n, h.nslots_dq, h.q0,
-                       h.qcsr_start, h.qcsr_slot, w.dq_slot, w.q, charges);
+    launch_batch_charges(h, nconf, w.dq_slot, w.q, charges);
     if (do_f || do_e)
         hipLaunchKernelGGL(k_b_pairs, dim3(nblk(n, kBatchI), nconf), dim3(kBatchJ), 0, h.stream, n, do_f ? 1 : 0,
                            do_e ? 1 : 0, h.ke, pos, w.q, h.lj, h.ex_start, h.ex_list, w.dedq, w.f_part, w.e_atom);

@@ -702,25 +702,7 @@ __global__ void __launch_bounds__(kWaveNL * kSeg) k_nlist_wave(DirectArgs a) {
 __device__ __forceinline__ void pair_term(PairAcc& acc, const DirectArgs& a, const double* __restrict__ tab,
                                           double4 pi, double2 li, double4 pj, double2 lj2, double dx, double dy,
                                           double dz, double r2) {
-    const double ke = a.ke;
-    const double two_over_sqrtpi = 1.1283791670955126;
-    double inv_r = rsqrt_fp64(r2);
-    double r = r2 * inv_r;
-    double ar = a.alpha * r;
-    double e2;
-    double ec = erfc_exp(ar, tab, a.erfc_scale, e2);
-    const double qj = ke * pj.w * inv_r;   // potential of j at i per unit erfc; qq = q_i qj
-    const double qq = pi.w * qj;
-    double sig = li.x + lj2.x;
-    double s2 = inv_r * sig; s2 *= s2;
-    const double sig6 = s2 * s2 * s2;
-    const double es6 = sig6 * li.y * lj2.y;
-    if (a.include_forces) {
-        const double dEdR = fma(qq, ec + ar * e2 * two_over_sqrtpi, es6 * (12 * sig6 - 6)) * (inv_r * inv_r);
-        acc.fx += dEdR * dx; acc.fy += dEdR * dy; acc.fz += dEdR * dz;
-        acc.dq += qj * ec;
-    }
-    acc.e += qq * ec + es6 * (sig6 - 1);   // the pair's full energy; halved once in store_pairs
+    ewald_pair(acc, a.ke, a.alpha, a.erfc_scale, a.include_forces, tab, pi.w, li, pj.w, lj2, dx, dy, dz, r2);
 }
 
 // stage the erfcx table in LDS (all threads of the block; call before any early return)
@@ -753,7 +735,6 @@ __device__ __forceinline__ void store_pairs(const PairAcc& acc, const DirectArgs
 __device__ __forceinline__ void excl_atom(const DirectArgs& a, int i, double3 add_f = make_double3(0.0, 0.0, 0.0),
                                           double add_dq = 0.0) {
     const double ke = a.ke;
-    const double two_over_sqrtpi = 1.1283791670955126;
     const int ex0 = a.ex_start[i], exc = a.ex_start[i + 1] - ex0;
     double fx = 0, fy = 0, fz = 0, dq = 0, ex_e = 0;
     if (a.include_forces) {
@@ -766,16 +747,7 @@ __device__ __forceinline__ void excl_atom(const DirectArgs& a, int i, double3 ad
         for (int k = 0; k < exc; k++) {
             int j = a.ex_list[ex0 + k];
             double3 d = delta_r(ld3(a.pos, j), xi, a.L, 1, a.T);
-            double r = sqrt(d.x * d.x + d.y * d.y + d.z * d.z);
-            double inv_r = 1.0 / r, ar = a.alpha * r;
-            double ef = erf(ar);
-            double qj = a.q[j];
-            if (a.include_forces) {
-                double g = ke * qi * qj * inv_r * inv_r * inv_r * (ef - ar * exp(-ar * ar) * two_over_sqrtpi);
-                fx -= g * d.x; fy -= g * d.y; fz -= g * d.z;
-                dq -= ke * qj * inv_r * ef;
-            }
-            ex_e -= 0.5 * ke * qi * qj * inv_r * ef;
+            CF_EXCL_PAIR(ke, a.alpha, a.include_forces, qi, a.q[j], d, fx, fy, fz, dq, ex_e)
         }
     }
     a.e_atom[3 * i + 2] = ex_e;

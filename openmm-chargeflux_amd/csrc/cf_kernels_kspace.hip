@@ -21,7 +21,7 @@
 #include <cstdlib>
 #include <stdexcept>
 
-#include "cf_internal.h"
+#include "cf_pair.h"
 
 namespace cf {
 
@@ -698,17 +698,8 @@ __global__ void __launch_bounds__(256) k_kvec(int64_t K, KGeom g, double3 rec, d
                                               double4* __restrict__ kv) {
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= K) return;
-    // enumerate the reference's half-space order RCK:519-556
-    int64_t a0 = g.KZ - 1;                       // nx=0, ny=0, nz=1..KZ-1
-    int64_t a1 = a0 + (int64_t)(g.KY - 1) * (2 * g.KZ - 1);  // nx=0, ny>=1
     int nx, ny, nz;
-    if (t < a0) { nx = 0; ny = 0; nz = (int)t + 1; }
-    else if (t < a1) { int64_t u = t - a0; nx = 0; ny = 1 + (int)(u / (2 * g.KZ - 1)); nz = (int)(u % (2 * g.KZ - 1)) - (g.KZ - 1); }
-    else {
-        int64_t u = t - a1; int64_t per = (int64_t)(2 * g.KY - 1) * (2 * g.KZ - 1);
-        nx = 1 + (int)(u / per); int64_t v = u % per;
-        ny = (int)(v / (2 * g.KZ - 1)) - (g.KY - 1); nz = (int)(v % (2 * g.KZ - 1)) - (g.KZ - 1);
-    }
+    half_space_k(t, g.KY, g.KZ, nx, ny, nz);
     double kx = nx * rec.x, ky = ny * rec.y, kz = nz * rec.z;
     double k2 = kx * kx + ky * ky + kz * kz;
     kv[t] = make_double4(kx, ky, kz, 2.0 * cst * exp(-k2 * 0.25 * one_4a2) / k2);

@@ -212,6 +212,69 @@ __device__ __forceinline__ double erfc_exp(double x, const double* __restrict__ 
     return e2 * p;
 }
 
+// real-space Ewald + LJ pair (RCK:567-592) seen from atom i, d = pos_i - pos_j (minimum image),
+// r2 = |d|^2 <= rc^2 (so alpha r lies inside the erfcx table tab, an LDS copy); charges qi, qj_,
+// LJ (sigma/2, 2 sqrt eps) li, lj2.  Adds the pair's FULL energy to acc.e (the callers halve it
+// once per atom) and, with forces, the force on i and dE/dq_i.  One definition for the list
+// kernels (cf_kernels_core.hip pair_term) and the batched periodic all-pairs kernel.
+__device__ __forceinline__ void ewald_pair(PairAcc& acc, double ke, double alpha, double erfc_scale, int include_forces,
+                                           const double* __restrict__ tab, double qi, double2 li, double qj_,
+                                           double2 lj2, double dx, double dy, double dz, double r2) {
+    const double two_over_sqrtpi = 1.1283791670955126;
+    double inv_r = rsqrt_fp64(r2);
+    double r = r2 * inv_r;
+    double ar = alpha * r;
+    double e2;
+    double ec = erfc_exp(ar, tab, erfc_scale, e2);
+    const double qj = ke * qj_ * inv_r;   // potential of j at i per unit erfc; qq = q_i qj
+    const double qq = qi * qj;
+    double sig = li.x + lj2.x;
+    double s2 = inv_r * sig; s2 *= s2;
+    const double sig6 = s2 * s2 * s2;
+    const double es6 = sig6 * li.y * lj2.y;
+    if (include_forces) {
+        const double dEdR = fma(qq, ec + ar * e2 * two_over_sqrtpi, es6 * (12 * sig6 - 6)) * (inv_r * inv_r);
+        acc.fx += dEdR * dx; acc.fy += dEdR * dy; acc.fz += dEdR * dz;
+        acc.dq += qj * ec;
+    }
+    acc.e += qq * ec + es6 * (sig6 - 1);
+}
+
+// erf correction of one excluded pair (RCK:596-622: minimum image d = pos_i - pos_j, no cutoff,
+// no LJ) seen from atom i: half the pair's energy to ex_e and, with forces, the force on i and
+// dE/dq_i (d: a double3; qj: the expression that yields the partner's charge, evaluated once, after
+// the erf).  One definition for k_excl (cf_kernels_core.hip excl_atom) and the batched periodic
+// kernel.  A statement macro, not an inline function: as a function the same body compiled k_excl to
+// different (30 instructions longer) code, and this form leaves k_excl's code object as it was.
+#define CF_EXCL_PAIR(ke, alpha, include_forces, qi, qj_expr, d, fx, fy, fz, dq, ex_e)                          \
+    {                                                                                                          \
+        const double two_over_sqrtpi = 1.1283791670955126;                                                     \
+        double r = sqrt(d.x * d.x + d.y * d.y + d.z * d.z);                                                    \
+        double inv_r = 1.0 / r, ar = (alpha) * r;                                                              \
+        double ef = erf(ar);                                                                                   \
+        double qj = (qj_expr);                                                                                 \
+        if (include_forces) {                                                                                  \
+            double g = ke * qi * qj * inv_r * inv_r * inv_r * (ef - ar * exp(-ar * ar) * two_over_sqrtpi);     \
+            fx -= g * d.x; fy -= g * d.y; fz -= g * d.z;                                                       \
+            dq -= ke * qj * inv_r * ef;                                                                        \
+        }                                                                                                      \
+        ex_e -= 0.5 * ke * qi * qj * inv_r * ef;                                                               \
+    }
+
+// k-vector t of the reference's half-space visiting order (RCK:519-556; KY, KZ = kmax_y, kmax_z):
+// (0, 0, 1..KZ-1), then (0, 1..KY-1, -(KZ-1)..KZ-1), then (1..KX-1, -(KY-1)..KY-1, -(KZ-1)..KZ-1)
+__device__ __forceinline__ void half_space_k(int64_t t, int KY, int KZ, int& nx, int& ny, int& nz) {
+    int64_t a0 = KZ - 1;                       // nx=0, ny=0, nz=1..KZ-1
+    int64_t a1 = a0 + (int64_t)(KY - 1) * (2 * KZ - 1);  // nx=0, ny>=1
+    if (t < a0) { nx = 0; ny = 0; nz = (int)t + 1; }
+    else if (t < a1) { int64_t u = t - a0; nx = 0; ny = 1 + (int)(u / (2 * KZ - 1)); nz = (int)(u % (2 * KZ - 1)) - (KZ - 1); }
+    else {
+        int64_t u = t - a1; int64_t per = (int64_t)(2 * KY - 1) * (2 * KZ - 1);
+        nx = 1 + (int)(u / per); int64_t v = u % per;
+        ny = (int)(v / (2 * KZ - 1)) - (KY - 1); nz = (int)(v % (2 * KZ - 1)) - (KZ - 1);
+    }
+}
+
 __device__ __forceinline__ unsigned long long to_fix(double v) {
     return (unsigned long long)(__double_as_longlong(fma(v, kFixScale, kFixMagic)) - kFixMagicBits);
 }

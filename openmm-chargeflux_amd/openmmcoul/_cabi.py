@@ -138,6 +138,9 @@ SIGNATURES = [
                                     C.c_int, C.c_void_p, C.c_void_p, C.c_int32]),
     ("cf_compute_batch", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cf_compute_batch_host", C.c_int, [C.c_void_p, C.c_int32, DP, C.c_int, DP, DP, DP]),
+    ("cf_compute_batch_periodic", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, DP, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    ("cf_compute_batch_periodic_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, C.c_int, DP, DP, DP]),
     ("cf_set_batch_limit", C.c_int, [C.c_void_p, C.c_int32]),
     ("cf_get_batch_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int64)]),

@@ -271,7 +271,7 @@ class HipCalcCoulForceKernel:
                                                 int(padded_n), _dp(b9), self._flags(includeForces, includeEnergy),
                                                 ptr(force_buffer), ptr(energy_buffer), ekind), self._lib)
 
-    # batched evaluation (cf_compute_batch: non-periodic systems, one rank) ------------------
+    # batched evaluation (cf_compute_batch: non-periodic systems; boxes=: periodic ones; one rank) ---
     def _check_batch_array(self, a, name, trailing, module=np):
         """(B,) + trailing, float64, C-contiguous -- checked before the C call."""
         shape = tuple(a.shape)
@@ -285,11 +285,27 @@ class HipCalcCoulForceKernel:
             raise ValueError(f"{name} must be a C-contiguous float64 array")
         return shape[0]
 
+    @staticmethod
+    def _batch_boxes(boxes, nconf):
+        """boxes of a periodic batch -> C-contiguous float64 (nconf, 3, 3) host array: (B, 3, 3), or
+        (3, 3) broadcast to every conformation -- checked before the C call."""
+        if not isinstance(boxes, np.ndarray) or boxes.dtype != np.float64 or not boxes.flags.c_contiguous:
+            raise ValueError("boxes must be a C-contiguous float64 numpy array (host memory)")
+        if boxes.shape == (3, 3):
+            return np.ascontiguousarray(np.broadcast_to(boxes, (nconf, 3, 3)))
+        if boxes.ndim != 3 or boxes.shape[1:] != (3, 3):
+            raise ValueError(f"boxes must have shape (B, 3, 3) or (3, 3), got {boxes.shape}")
+        if boxes.shape[0] != nconf:
+            raise ValueError(f"boxes holds {boxes.shape[0]} boxes for {nconf} conformations")
+        return boxes
+
     def execute_batch_host(self, positions, includeForces=True, includeEnergy=True, forces=None,
-                           return_charges=True):
+                           return_charges=True, *, boxes=None):
         """B conformations of the system in one call (cf_compute_batch_host): positions (B,N,3)
         float64 C-contiguous numpy array; forces (B,N,3) ADDED to (created if None).  Returns
-        (energies (B,), forces (B,N,3), charges (B,N) after flux, or None)."""
+        (energies (B,), forces (B,N,3), charges (B,N) after flux, or None).
+        boxes (periodic systems, cf_compute_batch_periodic_host): float64 numpy (B,3,3), one box
+        per conformation (rows a, b, c, OpenMM's reduced form), or (3,3) for all of them."""
         if not isinstance(positions, np.ndarray):
             raise ValueError("positions must be a numpy array of shape (B, N, 3)")
         nconf = self._check_batch_array(positions, "positions", (self._n, 3))
@@ -299,6 +315,12 @@ class HipCalcCoulForceKernel:
             raise ValueError("forces must be a float64 numpy array shaped like positions")
         energies = np.zeros(nconf)
         charges = np.zeros((nconf, self._n)) if return_charges else None
+        if boxes is not None:
+            b = self._batch_boxes(boxes, nconf)
+            _cabi.check(self._lib.cf_compute_batch_periodic_host(
+                self._h, nconf, _dp(positions), _dp(b), self._flags(includeForces, includeEnergy), _dp(forces),
+                _dp(energies), _dp(charges) if return_charges else None), self._lib)
+            return energies, forces, charges
         _cabi.check(self._lib.cf_compute_batch_host(self._h, nconf, _dp(positions),
                                                     self._flags(includeForces, includeEnergy), _dp(forces),
                                                     _dp(energies), _dp(charges) if return_charges else None),
@@ -306,10 +328,12 @@ class HipCalcCoulForceKernel:
         return energies, forces, charges
 
     def execute_batch_device(self, positions, includeForces, includeEnergy, forces=None, energies=None,
-                             charges=None):
+                             charges=None, *, boxes=None):
         """The same on torch tensors (float64, on the kernel's device, contiguous): positions
         (B,N,3); forces (B,N,3) ADDED to, energies (B,) and charges (B,N) overwritten; each output
-        may be None.  Asynchronous on the kernel's stream."""
+        may be None.  Asynchronous on the kernel's stream.
+        boxes (periodic systems, cf_compute_batch_periodic): as execute_batch_host -- a numpy array
+        in HOST memory here too, read during the call."""
         import torch
         if not isinstance(positions, torch.Tensor):
             raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
@@ -320,6 +344,12 @@ class HipCalcCoulForceKernel:
                                   or self._check_batch_array(t, name, trailing, torch) != nconf):
                 raise ValueError(f"{name} must be a float64 torch tensor for {nconf} conformations")
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if boxes is not None:
+            b = self._batch_boxes(boxes, nconf)
+            _cabi.check(self._lib.cf_compute_batch_periodic(
+                self._h, nconf, ptr(positions), _dp(b), self._flags(includeForces, includeEnergy), ptr(forces),
+                ptr(energies), ptr(charges)), self._lib)
+            return
         _cabi.check(self._lib.cf_compute_batch(self._h, nconf, ptr(positions),
                                                self._flags(includeForces, includeEnergy), ptr(forces),
                                                ptr(energies), ptr(charges)), self._lib)
