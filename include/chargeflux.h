@@ -31,7 +31,8 @@ extern "C" {
                               4: device index guards (cf_get_device_errors), cf_compute_openmm, octant list removed;
                               still 4 (purely additive): cf_compute_batch, cf_compute_batch_host,
                               cf_set_batch_limit, cf_get_batch_stats; cf_compute_batch_periodic,
-                              cf_compute_batch_periodic_host */
+                              cf_compute_batch_periodic_host; cf_get_param_counts, cf_compute_batch_vjp,
+                              cf_compute_batch_vjp_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -375,11 +376,58 @@ CF_EXPORT int cf_compute_batch_periodic(cf_handle* h, int32_t nconf, const doubl
 CF_EXPORT int cf_compute_batch_periodic_host(cf_handle* h, int32_t nconf, const double* pos_host,
                                              const double* boxes_host, int flags, double* forces_host,
                                              double* energy_host, double* charges_host);
+/*
+ * Parameter gradients of the non-periodic batch: the reverse-mode product (VJP) of cf_compute_batch
+ * with respect to the base charges and the flux parameters -- what an optimiser step of a
+ * charge-flux fit needs.  Per conformation, with the cotangents e_bar (scalar), q_bar[N] and
+ * F_bar[N][3] of its energy, its charges after flux and its forces, the call writes the gradient
+ * of  L = e_bar E + sum_i q_bar_i q_i + sum_i F_bar_i . F_i  with respect to every parameter.
+ *   counts[4]       N, 2 * bonds, 2 * angles, 5 * waters: the lengths of the four parameter groups;
+ *                   P = their sum
+ *   pos_dev         [nconf][N][3] fp64 DEVICE, conformation-major
+ *   energy_bar_dev  [nconf] fp64 DEVICE, or NULL (= zero)
+ *   charges_bar_dev [nconf][N] fp64 DEVICE, or NULL (= zero)
+ *   forces_bar_dev  [nconf][N][3] fp64 DEVICE, or NULL (= zero)
+ *   grad_dev        [nconf][P] fp64 DEVICE, OVERWRITTEN: per conformation the base charges [N], then
+ *                   the bonds' (k, b) pairs, the angles' (k, theta0) pairs and the waters'
+ *                   (k1, k2, kub, b0, ub0) 5-tuples -- the order and layout of the cf_params arrays
+ * The gradients of the conformations are NOT summed: a fit sums them with its own weights.  With all
+ * three cotangents NULL grad is set to exact zeros (one memset, no pass).
+ * Closed form (every flux term is linear in each of its parameters, the energy quadratic in the
+ * charges): with g_i = dE/dq_i, h_i the directional derivative of g_i along F_bar and
+ * a_i = e_bar g_i + q_bar_i - h_i, the base charge i receives a_i and every flux parameter a
+ * product of the a and g of its term's atoms with the term's geometry and its tangent along F_bar
+ * ("Batched, parameter gradients").  No formula divides by a parameter: a term with
+ * k = 0 is legal.
+ * Out of scope: periodic handles (CF_ERR_INVALID, as cf_compute_batch), gradients with respect to
+ * the LJ sigma / epsilon, and gradients with respect to the positions.
+ * Errors and states as cf_compute_batch: a periodic handle CF_ERR_INVALID; world_size > 1 or a call
+ * between cf_compute_begin and _end CF_ERR_STATE; NULL pos or grad, or nconf < 0, CF_ERR_INVALID;
+ * nconf = 0 is a no-op; a NULL handle is rejected without touching a device.
+ * Always fp64, eager launches on the handle's stream (never captured or replayed, not recorded by
+ * cf_set_timing), asynchronous: inputs and outputs must stay valid until the stream reaches them.  A
+ * pass is at most five kernel launches whatever nconf, without atomics; every sum's order depends
+ * only on N and the topology, so a conformation's gradients are bitwise the same alone, at any
+ * position of any batch and under any pass size.  It uses the batch workspace and, allocated on the
+ * first call (growth allocates and synchronises; cf_destroy frees it), three more arrays of N doubles
+ * per conformation; cf_compute's state and diagnostics are not touched.  It reads the parameter
+ * buffers cf_update_parameters last wrote.  No guard bits.
+ */
+CF_EXPORT int cf_get_param_counts(const cf_handle* h, int32_t counts[4]);
+CF_EXPORT int cf_compute_batch_vjp(cf_handle* h, int32_t nconf, const double* pos_dev,
+                                   const double* energy_bar_dev, const double* charges_bar_dev,
+                                   const double* forces_bar_dev, double* grad_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_vjp_host(cf_handle* h, int32_t nconf, const double* pos_host,
+                                        const double* energy_bar_host, const double* charges_bar_host,
+                                        const double* forces_bar_host, double* grad_host);
 /* cap on the conformations evaluated per pass (bounds the batch workspace); 0 = automatic: as many
  * as keep the workspace (per conformation q[N], the flux slots, dq/dx, dE/dq[N], F[3N], e[N]; a
  * periodic batch also the phase tables, 4 doubles per [N][kmax_x + kmax_y + kmax_z] entry, and 3
- * doubles per k-vector) at or below 256 MiB, and never more than 65535.  A larger batch runs as consecutive
- * passes.  Applies to both batch forms; cf_get_batch_stats counts both. */
+ * doubles per k-vector; cf_compute_batch_vjp also qdot[N], g[N], a[N]) at or below 256 MiB, and never
+ * more than 65535.  A larger batch runs as consecutive passes.  Applies to every batch form;
+ * cf_get_batch_stats counts them all (a cf_compute_batch_vjp with all cotangents NULL counts its
+ * call and conformations, and no pass). */
 CF_EXPORT int cf_set_batch_limit(cf_handle* h, int32_t max_conformations);
 /* since cf_create: batch calls, conformations evaluated, passes (chunks) launched; any output may be NULL */
 CF_EXPORT int cf_get_batch_stats(const cf_handle* h, int64_t* calls, int64_t* conformations, int64_t* passes);

@@ -73,6 +73,11 @@ struct cf_handle {
     double* batch_boxes_dev = nullptr;   // [batch_boxes_cap][8] device (in H->allocs)
     int64_t batch_boxes_cap = 0;
     hipEvent_t batch_boxes_ev = nullptr;
+    // cf_compute_batch_vjp: the extra workspace beside `batch` (qdot, g, a) and the host form's
+    // staging (pos, the three cotangents, grad); both in H->allocs
+    cf::BatchGradWs batch_grad;
+    double* batch_grad_stage = nullptr;
+    int64_t batch_grad_stage_confs = 0;
 };
 
 namespace {
@@ -1996,6 +2001,116 @@ CF_EXPORT int cf_compute_batch_periodic_host(cf_handle* H, int32_t nconf, const 
         check_hip(hipStreamSynchronize(h.stream), "sync");
         if (fw)
             for (size_t k = 0; k < f.size(); k++) forces_host[k] += f[k];
+    });
+}
+
+// ---- parameter gradients of the non-periodic batch (cf_kernels_batch_grad.hip) ---------------------
+CF_EXPORT int cf_get_param_counts(const cf_handle* H, int32_t counts[4]) {
+    if (!H || !counts) { g_err = "null argument"; return CF_ERR_INVALID; }
+    counts[0] = H->h.n; counts[1] = 2 * H->h.nb; counts[2] = 2 * H->h.na; counts[3] = 5 * H->h.nw;
+    return CF_OK;
+}
+
+// Everything that can refuse the call, before anything is launched, staged or counted.
+static void batch_vjp_precheck(cf_handle* H, int32_t nconf, const double* pos, const double* grad, const char* name) {
+    if (!H || !pos || !grad) fail(CF_ERR_INVALID, "null argument");
+    if (nconf < 0) fail(CF_ERR_INVALID, "nconf must be >= 0");
+    cf::Handle& h = H->h;
+    if (h.world > 1) fail(CF_ERR_STATE, std::string(name) + " is single-rank only");
+    if (h.pbc) fail(CF_ERR_INVALID, std::string(name) + ": batches are non-periodic only (this handle is periodic)");
+    if (h.pending_flags >= 0) fail(CF_ERR_STATE, std::string(name) + " during a begun evaluation");
+    guard_check(h);
+}
+
+// the pass keeps the forward workspace and qdot, g, a together at or below kBatchAutoBytes
+static int batch_vjp_pass_size(const cf_handle* H, int nconf) {
+    const size_t per = (cf::batch_doubles_per_conf(H->h) + cf::batch_grad_doubles_per_conf(H->h)) * sizeof(double);
+    int64_t lim = H->batch_limit > 0 ? H->batch_limit : (int64_t)std::max<size_t>(1, kBatchAutoBytes / per);
+    lim = std::min<int64_t>(lim, cf::kBatchMaxPass);
+    return (int)std::min<int64_t>(lim, nconf);
+}
+
+CF_EXPORT int cf_compute_batch_vjp(cf_handle* H, int32_t nconf, const double* pos_dev, const double* energy_bar_dev,
+                                   const double* charges_bar_dev, const double* forces_bar_dev, double* grad_dev) {
+    return guarded([&] {
+        batch_vjp_precheck(H, nconf, pos_dev, grad_dev, "cf_compute_batch_vjp");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        if (!energy_bar_dev && !charges_bar_dev && !forces_bar_dev) {   // zero cotangent: exact zeros, no pass
+            check_hip(hipMemsetAsync(grad_dev, 0, sizeof(double) * np * (size_t)nconf, h.stream), "memset grad");
+            return;
+        }
+        const int pass = batch_vjp_pass_size(H, nconf);
+        if (pass > H->batch.cap) {   // first call or growth: allocates (and so synchronises)
+            double* old = H->batch.base;
+            H->batch = cf::BatchWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_carve(h, base, pass, H->batch);
+        }
+        if (pass > H->batch_grad.cap) {
+            double* old = H->batch_grad.base;
+            H->batch_grad = cf::BatchGradWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_grad_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_grad_carve(h, base, pass, H->batch_grad);
+        }
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events (as cf_compute_batch)
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            cf::launch_batch_vjp(h, H->batch, H->batch_grad, m, pos_dev + 3 * n * c0,
+                                 energy_bar_dev ? energy_bar_dev + c0 : nullptr,
+                                 charges_bar_dev ? charges_bar_dev + n * c0 : nullptr,
+                                 forces_bar_dev ? forces_bar_dev + 3 * n * c0 : nullptr, grad_dev + np * c0);
+            H->batch_passes++;
+        }
+        launch_check(h, "compute_batch_vjp");
+    });
+}
+
+CF_EXPORT int cf_compute_batch_vjp_host(cf_handle* H, int32_t nconf, const double* pos_host,
+                                        const double* energy_bar_host, const double* charges_bar_host,
+                                        const double* forces_bar_host, double* grad_host) {
+    return guarded([&] {
+        batch_vjp_precheck(H, nconf, pos_host, grad_host, "cf_compute_batch_vjp_host");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, B = (size_t)nconf;
+        const size_t np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+        if (nconf > H->batch_grad_stage_confs) {
+            double* old = H->batch_grad_stage;
+            H->batch_grad_stage = nullptr; H->batch_grad_stage_confs = 0;
+            dfree(H, old);
+            H->batch_grad_stage = dalloc<double>(H, B * (3 * n + 1 + n + 3 * n + np));
+            H->batch_grad_stage_confs = nconf;
+        }
+        double* pos = H->batch_grad_stage;
+        double* eb = pos + 3 * n * B;
+        double* qb = eb + B;
+        double* fb = qb + n * B;
+        double* grad = fb + 3 * n * B;
+        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D positions");
+        if (energy_bar_host)
+            check_hip(hipMemcpyAsync(eb, energy_bar_host, sizeof(double) * B, hipMemcpyHostToDevice, h.stream),
+                      "H2D energy cotangent");
+        if (charges_bar_host)
+            check_hip(hipMemcpyAsync(qb, charges_bar_host, sizeof(double) * n * B, hipMemcpyHostToDevice, h.stream),
+                      "H2D charge cotangent");
+        if (forces_bar_host)
+            check_hip(hipMemcpyAsync(fb, forces_bar_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                      "H2D force cotangent");
+        const int rc = cf_compute_batch_vjp(H, nconf, pos, energy_bar_host ? eb : nullptr, charges_bar_host ? qb : nullptr,
+                                            forces_bar_host ? fb : nullptr, grad);
+        if (rc != CF_OK) throw CfError(rc, g_err);
+        check_hip(hipMemcpyAsync(grad_host, grad, sizeof(double) * np * B, hipMemcpyDeviceToHost, h.stream), "D2H grad");
+        check_hip(hipStreamSynchronize(h.stream), "sync");
     });
 }
 

@@ -336,6 +336,26 @@ void launch_batch(Handle& h, const BatchWs& w, int nconf, const double* pos, int
                   double* energy, double* charges);
 
 void launch_batch_charges(Handle& h, int nconf, const double* dq_slot, double* q, double* charges);   // k_b_charges
+// k_b_flux + k_b_charges of one pass into w (q, dq slots, dq/dx): the first two launches of launch_batch
+void launch_batch_flux_charges(Handle& h, const BatchWs& w, int nconf, const double* pos, double* charges);
+
+// parameter gradients of the non-periodic batch (cf_kernels_batch_grad.hip, cf_compute_batch_vjp):
+// the extra workspace of one pass beside BatchWs, carved from one allocation of
+// cap * batch_grad_doubles_per_conf doubles
+struct BatchGradWs {
+    double* base = nullptr;
+    int cap = 0;                // conformations the arrays hold
+    double* qdot = nullptr;     // [cap][N] tangent of the charges along the force cotangent
+    double* g = nullptr;        // [cap][N] dE/dq
+    double* a = nullptr;        // [cap][N] adjoint weight e_bar g + q_bar - h
+};
+size_t batch_grad_doubles_per_conf(const Handle& h);
+void batch_grad_carve(const Handle& h, double* base, int cap, BatchGradWs& w);
+// one pass of nconf <= min(w.cap, gw.cap) conformations on h.stream: at most five launches, whatever
+// nconf.  e_bar [nconf], q_bar [nconf][N], f_bar [nconf][N][3]: device or null (= zero);
+// grad [nconf][N + 2 nb + 2 na + 5 nw] overwritten
+void launch_batch_vjp(Handle& h, const BatchWs& w, const BatchGradWs& gw, int nconf, const double* pos,
+                      const double* e_bar, const double* q_bar, const double* f_bar, double* grad);
 
 // batched periodic evaluation (cf_kernels_batch_pbc.hip, cf_compute_batch_periodic): one box per
 // conformation, all pairs by minimum image + the exact k-sum.  Workspace of one pass, carved from

@@ -195,6 +195,13 @@ void launch_batch_charges(Handle& h, int nconf, const double* dq_slot, double* q
                        h.qcsr_start, h.qcsr_slot, dq_slot, q, charges);
 }
 
+void launch_batch_flux_charges(Handle& h, const BatchWs& w, int nconf, const double* pos, double* charges) {
+    if (h.nterms > 0)
+        hipLaunchKernelGGL(k_b_flux, dim3(nblk((int64_t)nconf * h.nterms, 256)), dim3(256), 0, h.stream, nconf, h.n,
+                           h.nterms, h.nb, h.na, h.nslots_dq, 3L * h.nd, h.term_idx, h.term_par, pos, w.dq_slot, w.dqdx);
+    launch_batch_charges(h, nconf, w.dq_slot, w.q, charges);
+}
+
 void launch_batch(Handle& h, const BatchWs& w, int nconf, const double* pos, int flags, double* forces,
                   double* energy, double* charges) {
     if (nconf <= 0 || nconf > w.cap || nconf > kBatchMaxPass) throw std::invalid_argument("launch_batch: pass size");
@@ -202,10 +209,7 @@ void launch_batch(Handle& h, const BatchWs& w, int nconf, const double* pos, int
     const bool do_f = (flags & CF_INCLUDE_FORCES) && forces;
     const bool do_e = (flags & CF_INCLUDE_ENERGY) && energy;
     const long nd3 = 3L * h.nd;
-    if (h.nterms > 0)
-        hipLaunchKernelGGL(k_b_flux, dim3(nblk((int64_t)nconf * h.nterms, 256)), dim3(256), 0, h.stream, nconf, n,
-                           h.nterms, h.nb, h.na, h.nslots_dq, nd3, h.term_idx, h.term_par, pos, w.dq_slot, w.dqdx);
-    launch_batch_charges(h, nconf, w.dq_slot, w.q, charges);
+    launch_batch_flux_charges(h, w, nconf, pos, charges);
     if (do_f || do_e)
         hipLaunchKernelGGL(k_b_pairs, dim3(nblk(n, kBatchI), nconf), dim3(kBatchJ), 0, h.stream, n, do_f ? 1 : 0,
                            do_e ? 1 : 0, h.ke, pos, w.q, h.lj, h.ex_start, h.ex_list, w.dedq, w.f_part, w.e_atom);

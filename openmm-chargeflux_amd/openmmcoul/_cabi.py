@@ -144,6 +144,10 @@ SIGNATURES = [
     ("cf_set_batch_limit", C.c_int, [C.c_void_p, C.c_int32]),
     ("cf_get_batch_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int64)]),
+    ("cf_get_param_counts", C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    ("cf_compute_batch_vjp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    ("cf_compute_batch_vjp_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP, DP, DP]),
 ]
 
 _lib = None

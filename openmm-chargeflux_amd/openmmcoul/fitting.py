@@ -1,0 +1,113 @@
+"""Fitting a charge-flux model: the batched evaluation as a differentiable torch function of the
+base charges and the flux parameters.
+
+    model = BatchedChargeFlux(kernel, force)          # kernel initialised with force, non-periodic
+    energies, forces, charges = model(q, bonds, angles, waters, positions)
+    loss = ((forces - target) ** 2).mean()
+    loss.backward()                                   # q.grad, bonds.grad, angles.grad, waters.grad
+
+Forward is cf_compute_batch, backward one cf_compute_batch_vjp (include/chargeflux.h): both run in
+libchargeflux_hip.so.  Gradients exist for the parameters only -- not for the positions, and not for
+the LJ sigma / epsilon, which are taken from `force` unchanged.
+"""
+from __future__ import annotations
+
+import torch
+
+from .force import CoulForce
+from .kernel import HipCalcCoulForceKernel
+
+
+class _BatchFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, charges, bonds, angles, waters, positions):
+        params = tuple(t.detach().to("cpu", torch.float64).contiguous() for t in (charges, bonds, angles, waters))
+        model._load(params)
+        k = model.kernel
+        nconf, n = positions.shape[0], positions.shape[1]
+        energies = torch.empty(nconf, dtype=torch.float64, device=positions.device)
+        forces = torch.zeros((nconf, n, 3), dtype=torch.float64, device=positions.device)
+        q = torch.empty((nconf, n), dtype=torch.float64, device=positions.device)
+        model._before()
+        k.execute_batch_device(positions, True, True, forces, energies, q)
+        model._after()
+        ctx.set_materialize_grads(False)   # an output the loss does not use: a None (NULL) cotangent
+        ctx.model, ctx.params, ctx.loaded = model, params, model._loads
+        ctx.inputs = (charges, bonds, angles, waters)
+        ctx.save_for_backward(positions)
+        return energies, forces, q
+
+    @staticmethod
+    def backward(ctx, e_bar, f_bar, q_bar):
+        model = ctx.model
+        k = model.kernel
+        (positions,) = ctx.saved_tensors
+        if model._loads != ctx.loaded:   # another forward has changed the parameters since: put these back
+            model._load(ctx.params)
+            ctx.loaded = model._loads
+        counts = k.param_counts()
+        grad = torch.empty((positions.shape[0], sum(counts)), dtype=torch.float64, device=positions.device)
+        cot = [None if t is None else t.detach().to(torch.float64).contiguous() for t in (e_bar, q_bar, f_bar)]
+        model._before()
+        k.execute_batch_vjp_device(positions, grad, *cot)
+        model._after()
+        g = k.split_gradient(grad.sum(dim=0, keepdim=True), counts)
+        out = []
+        for t, name, need in zip(ctx.inputs, ("charges", "bonds", "angles", "waters"), ctx.needs_input_grad[1:5]):
+            out.append(g[name][0].reshape(t.shape).to(t.device) if need else None)
+        return (None, *out, None)
+
+
+class BatchedChargeFlux:
+    """Energies, forces and charges of B conformations as a differentiable function of the
+    parameters.  kernel: a HipCalcCoulForceKernel initialised with `force` (non-periodic, one rank);
+    force: the CoulForce whose topology, sigma and epsilon are used -- its charges and flux
+    parameters are overwritten by every call.
+
+    __call__(charges (N,), bonds (nb,2), angles (na,2), waters (nw,5), positions (B,N,3)):
+    float64 tensors, the parameters on any device, positions contiguous on the kernel's device and
+    not requiring grad.  Returns (energies (B,), forces (B,N,3), charges (B,N)) on that device.
+    The parameter rows are the cf_params rows: bonds (k, b), angles (k, theta0), waters
+    (k1, k2, kub, b0, ub0).  A kernel on a stream of its own is synchronised with torch's current
+    stream around each call."""
+
+    def __init__(self, kernel: HipCalcCoulForceKernel, force: CoulForce):
+        self.kernel, self.force = kernel, force
+        self._loads = 0
+
+    def parameters(self, device=None):
+        """The force's current parameters as four leaf tensors (requires_grad) on `device`."""
+        a = self.force.arrays()
+        return tuple(torch.tensor(a[key], dtype=torch.float64, device=device, requires_grad=True)
+                     for key in ("charges", "fbond_par", "fangle_par", "fwater_par"))
+
+    def _load(self, params):
+        q, bonds, angles, waters = (p.numpy() for p in params)
+        f = self.force
+        shapes = ((f.getNumParticles(),), (f.getNumFluxBonds(), 2), (f.getNumFluxAngles(), 2), (f.getNumFluxWaters(), 5))
+        for p, name, shape in zip((q, bonds, angles, waters), ("charges", "bonds", "angles", "waters"), shapes):
+            if tuple(p.shape) != shape:
+                raise ValueError(f"{name} must have shape {shape}, got {tuple(p.shape)}")
+        f._charges = [float(v) for v in q]
+        f._fbond_par = [tuple(float(v) for v in row) for row in bonds]
+        f._fangle_par = [tuple(float(v) for v in row) for row in angles]
+        f._fwater_par = [tuple(float(v) for v in row) for row in waters]
+        self.kernel.copyParametersToContext(f)
+        self._loads += 1
+
+    def _before(self):
+        if self.kernel._stream:   # the kernel's own stream: the inputs torch has queued must exist
+            torch.cuda.current_stream().synchronize()
+
+    def _after(self):
+        if self.kernel._stream:
+            self.kernel.synchronize()
+
+    def __call__(self, charges, bonds, angles, waters, positions):
+        for t, name in ((charges, "charges"), (bonds, "bonds"), (angles, "angles"), (waters, "waters"),
+                        (positions, "positions")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise ValueError(f"{name} must be a float64 torch tensor")
+        if positions.requires_grad:
+            raise ValueError("positions must not require grad: gradients with respect to positions are not computed")
+        return _BatchFn.apply(self, charges, bonds, angles, waters, positions)

@@ -354,6 +354,65 @@ class HipCalcCoulForceKernel:
                                                self._flags(includeForces, includeEnergy), ptr(forces),
                                                ptr(energies), ptr(charges)), self._lib)
 
+    # parameter gradients of the non-periodic batch (cf_compute_batch_vjp) --------------------------
+    def param_counts(self):
+        """(N, 2 * bonds, 2 * angles, 5 * waters): the lengths of the four parameter groups of a
+        gradient row (cf_get_param_counts); P is their sum."""
+        c = (C.c_int32 * 4)()
+        _cabi.check(self._lib.cf_get_param_counts(self._h, c), self._lib)
+        return tuple(c)
+
+    def _check_cotangents(self, nconf, energy_bar, charges_bar, forces_bar, module, kind):
+        for t, name, trailing in ((energy_bar, "energy_bar", ()), (charges_bar, "charges_bar", (self._n,)),
+                                  (forces_bar, "forces_bar", (self._n, 3))):
+            if t is not None and (not isinstance(t, kind)
+                                  or self._check_batch_array(t, name, trailing, module) != nconf):
+                raise ValueError(f"{name} must be a float64 {kind.__name__} for {nconf} conformations")
+
+    def execute_batch_vjp_host(self, positions, energy_bar=None, charges_bar=None, forces_bar=None):
+        """Gradients of L = energy_bar . E + charges_bar . q + forces_bar . F with respect to the base
+        charges and the flux parameters, per conformation (cf_compute_batch_vjp_host; non-periodic
+        systems).  positions (B,N,3), energy_bar (B,), charges_bar (B,N), forces_bar (B,N,3):
+        C-contiguous float64 numpy arrays, a cotangent may be None (= zero).  Returns a dict:
+        charges (B,N), bonds (B,nb,2) as (k, b), angles (B,na,2) as (k, theta0), waters (B,nw,5) as
+        (k1, k2, kub, b0, ub0) -- views of one (B,P) array, which is returned as flat."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        self._check_cotangents(nconf, energy_bar, charges_bar, forces_bar, np, np.ndarray)
+        counts = self.param_counts()
+        flat = np.zeros((nconf, sum(counts)))
+        opt = lambda a: _dp(a) if a is not None else None
+        _cabi.check(self._lib.cf_compute_batch_vjp_host(self._h, nconf, _dp(positions), opt(energy_bar),
+                                                        opt(charges_bar), opt(forces_bar), _dp(flat)), self._lib)
+        return self.split_gradient(flat, counts)
+
+    @staticmethod
+    def split_gradient(flat, counts):
+        """Views of a (B,P) gradient array (numpy or torch) by parameter group."""
+        n, b2, a2, w5 = counts
+        nconf = flat.shape[0]
+        o1, o2, o3 = n, n + b2, n + b2 + a2
+        return {"flat": flat, "charges": flat[:, :o1], "bonds": flat[:, o1:o2].reshape(nconf, b2 // 2, 2),
+                "angles": flat[:, o2:o3].reshape(nconf, a2 // 2, 2),
+                "waters": flat[:, o3:o3 + w5].reshape(nconf, w5 // 5, 5)}
+
+    def execute_batch_vjp_device(self, positions, grad, energy_bar=None, charges_bar=None, forces_bar=None):
+        """The same on torch tensors (float64, on the kernel's device, contiguous): grad (B,P) is
+        overwritten (split_gradient gives its views).  Asynchronous on the kernel's stream."""
+        import torch
+        if not isinstance(positions, torch.Tensor):
+            raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
+        self._check_cotangents(nconf, energy_bar, charges_bar, forces_bar, torch, torch.Tensor)
+        if not isinstance(grad, torch.Tensor):
+            raise ValueError("grad must be a torch tensor of shape (B, P)")
+        if self._check_batch_array(grad, "grad", (sum(self.param_counts()),), torch) != nconf:
+            raise ValueError(f"grad must hold {nconf} conformations")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _cabi.check(self._lib.cf_compute_batch_vjp(self._h, nconf, ptr(positions), ptr(energy_bar), ptr(charges_bar),
+                                                   ptr(forces_bar), ptr(grad)), self._lib)
+
     def set_batch_limit(self, n: int):
         """Conformations evaluated per pass of a batch (bounds the batch workspace); 0 = automatic
         (a 256 MiB workspace).  Results do not depend on it."""
