@@ -32,7 +32,8 @@ extern "C" {
                               still 4 (purely additive): cf_compute_batch, cf_compute_batch_host,
                               cf_set_batch_limit, cf_get_batch_stats; cf_compute_batch_periodic,
                               cf_compute_batch_periodic_host; cf_get_param_counts, cf_compute_batch_vjp,
-                              cf_compute_batch_vjp_host */
+                              cf_compute_batch_vjp_host; cf_compute_batch_periodic_vjp,
+                              cf_compute_batch_periodic_vjp_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -399,8 +400,8 @@ CF_EXPORT int cf_compute_batch_periodic_host(cf_handle* h, int32_t nconf, const 
  * product of the a and g of its term's atoms with the term's geometry and its tangent along F_bar
  * ("Batched, parameter gradients").  No formula divides by a parameter: a term with
  * k = 0 is legal.
- * Out of scope: periodic handles (CF_ERR_INVALID, as cf_compute_batch), gradients with respect to
- * the LJ sigma / epsilon, and gradients with respect to the positions.
+ * Periodic handles have cf_compute_batch_periodic_vjp (here: CF_ERR_INVALID, as cf_compute_batch).
+ * Out of scope: gradients with respect to the LJ sigma / epsilon and to the positions.
  * Errors and states as cf_compute_batch: a periodic handle CF_ERR_INVALID; world_size > 1 or a call
  * between cf_compute_begin and _end CF_ERR_STATE; NULL pos or grad, or nconf < 0, CF_ERR_INVALID;
  * nconf = 0 is a no-op; a NULL handle is rejected without touching a device.
@@ -421,13 +422,52 @@ CF_EXPORT int cf_compute_batch_vjp(cf_handle* h, int32_t nconf, const double* po
 CF_EXPORT int cf_compute_batch_vjp_host(cf_handle* h, int32_t nconf, const double* pos_host,
                                         const double* energy_bar_host, const double* charges_bar_host,
                                         const double* forces_bar_host, double* grad_host);
+/*
+ * The same for a PERIODIC handle, one box per conformation: the reverse-mode product of
+ * cf_compute_batch_periodic with respect to the base charges and the flux parameters.  Cotangents
+ * and grad as cf_compute_batch_vjp (rows in the order of cf_get_param_counts, not summed over the
+ * conformations, NULL cotangents = zeros, all three NULL = one memset of grad); boxes_host
+ * [nconf][9] fp64 HOST as cf_compute_batch_periodic: copied through the handle's pinned buffer and
+ * uploaded (the same reuse rule), every box checked by cf_compute's rules before anything is
+ * launched -- a bad box gives CF_ERR_INVALID with a message naming the conformation index, no output
+ * touched, no statistic counted.
+ * The scalar differentiated per conformation is L = e_bar E + sum_i q_bar_i q_i + sum_i F_bar_i . F_i
+ * with E, q, F what cf_compute_batch_periodic returns for that conformation and box with both
+ * CF_INCLUDE_* flags (all four energy terms): fp64, the exact k-sum over the half-space k set, all
+ * pairs by minimum image; alpha and kmax are cf_create's, the Coulomb constant the handle's.  Closed
+ * form as cf_compute_batch_vjp, with g_i and h_i now summing the erfc pair terms within the cutoff,
+ * the erf correction of excluded pairs, the self term and the reciprocal sum with the structure
+ * factor S(k) and its tangent along F_bar, and the term geometry taken from minimum-image vectors
+ * ("Batched, periodic, parameter gradients").  The box is fixed: no box derivatives.  No
+ * formula divides by a parameter.
+ * A non-periodic handle gives CF_ERR_INVALID; world_size > 1 or a call between cf_compute_begin and
+ * _end CF_ERR_STATE; NULL pos, boxes or grad, or nconf < 0, CF_ERR_INVALID; nconf = 0 is a no-op
+ * that counts nothing; a NULL handle is rejected without touching a device.
+ * Eager launches on the handle's stream (never captured or replayed, not recorded by
+ * cf_set_timing), asynchronous.  A pass is at most eight kernel launches whatever nconf, without
+ * atomics; every sum's order depends only on N, the topology and kmax, so a conformation's gradients
+ * are bitwise the same alone, at any position of any batch and under any pass size.  It uses the
+ * periodic batch workspace and, allocated on the first call (growth allocates and synchronises;
+ * cf_destroy frees it), a block of its own: qdot[N], g[N], a[N] and a second coefficient array of 2
+ * doubles per k-vector per conformation.  cf_compute's state and diagnostics are not touched.  It
+ * reads the parameter buffers cf_update_parameters last wrote.  No guard bits.
+ */
+CF_EXPORT int cf_compute_batch_periodic_vjp(cf_handle* h, int32_t nconf, const double* pos_dev,
+                                            const double* boxes_host, const double* energy_bar_dev,
+                                            const double* charges_bar_dev, const double* forces_bar_dev,
+                                            double* grad_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_periodic_vjp_host(cf_handle* h, int32_t nconf, const double* pos_host,
+                                                 const double* boxes_host, const double* energy_bar_host,
+                                                 const double* charges_bar_host, const double* forces_bar_host,
+                                                 double* grad_host);
 /* cap on the conformations evaluated per pass (bounds the batch workspace); 0 = automatic: as many
  * as keep the workspace (per conformation q[N], the flux slots, dq/dx, dE/dq[N], F[3N], e[N]; a
  * periodic batch also the phase tables, 4 doubles per [N][kmax_x + kmax_y + kmax_z] entry, and 3
- * doubles per k-vector; cf_compute_batch_vjp also qdot[N], g[N], a[N]) at or below 256 MiB, and never
- * more than 65535.  A larger batch runs as consecutive passes.  Applies to every batch form;
- * cf_get_batch_stats counts them all (a cf_compute_batch_vjp with all cotangents NULL counts its
- * call and conformations, and no pass). */
+ * doubles per k-vector; cf_compute_batch_vjp also qdot[N], g[N], a[N]; cf_compute_batch_periodic_vjp
+ * those three and 2 more doubles per k-vector) at or below 256 MiB, and never more than 65535.  A
+ * larger batch runs as consecutive passes.  Applies to every batch form; cf_get_batch_stats counts
+ * them all (a VJP call with all cotangents NULL counts its call and conformations, and no pass). */
 CF_EXPORT int cf_set_batch_limit(cf_handle* h, int32_t max_conformations);
 /* since cf_create: batch calls, conformations evaluated, passes (chunks) launched; any output may be NULL */
 CF_EXPORT int cf_get_batch_stats(const cf_handle* h, int64_t* calls, int64_t* conformations, int64_t* passes);

@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <numeric>
 #include <stdexcept>
 #include <string>
@@ -78,6 +79,9 @@ struct cf_handle {
     cf::BatchGradWs batch_grad;
     double* batch_grad_stage = nullptr;
     int64_t batch_grad_stage_confs = 0;
+    // cf_compute_batch_periodic_vjp: the extra workspace beside `batch_pbc` (the second coefficient
+    // array, qdot, g, a), in H->allocs; its host form stages through batch_grad_stage
+    cf::BatchPbcGradWs batch_pbc_grad;
 };
 
 namespace {
@@ -1880,12 +1884,12 @@ CF_EXPORT int cf_compute_batch_host(cf_handle* H, int32_t nconf, const double* p
 // ---- batched periodic evaluation (one box per conformation; cf_kernels_batch_pbc.hip) -------------
 // Everything that can refuse the call, before anything is launched, staged or counted.
 static void batch_periodic_precheck(cf_handle* H, int32_t nconf, const double* pos, const double* boxes_host,
-                                    const char* name) {
+                                    const char* name, const char* nonperiodic = "cf_compute_batch") {
     if (!H || !pos || !boxes_host) fail(CF_ERR_INVALID, "null argument");
     if (nconf < 0) fail(CF_ERR_INVALID, "nconf must be >= 0");
     cf::Handle& h = H->h;
     if (h.world > 1) fail(CF_ERR_STATE, std::string(name) + " is single-rank only");
-    if (!h.pbc) fail(CF_ERR_INVALID, std::string(name) + ": this handle is not periodic (use cf_compute_batch)");
+    if (!h.pbc) fail(CF_ERR_INVALID, std::string(name) + ": this handle is not periodic (use " + nonperiodic + ")");
     if (h.pending_flags >= 0) fail(CF_ERR_STATE, std::string(name) + " during a begun evaluation");
     guard_check(h);
     // every box by the rules of set_box, all of them before the first launch
@@ -1898,6 +1902,35 @@ static void batch_periodic_precheck(cf_handle* H, int32_t nconf, const double* p
             if (h.cutoff > 0.5 * L[d] * (1 + 1e-12))
                 fail(CF_ERR_INVALID, what + ": cutoff exceeds half the periodic box (minimum image would be ambiguous)");
     }
+}
+
+// The boxes of a periodic batch call: (Lx, Ly, Lz, bx, cx, cy, 0, 0) per conformation into the pinned
+// copy, one upload to batch_boxes_dev for the whole call.  The pinned copy of the previous call is
+// reused once its upload is done (a wait for that copy, which the stream reached before the previous
+// call's kernels).
+static void batch_boxes_upload(cf_handle* H, int32_t nconf, const double* boxes_host) {
+    cf::Handle& h = H->h;
+    if (!H->batch_boxes_ev) check_hip(hipEventCreateWithFlags(&H->batch_boxes_ev, hipEventDisableTiming), "hipEventCreate");
+    else check_hip(hipEventSynchronize(H->batch_boxes_ev), "hipEventSynchronize (boxes)");
+    if (nconf > H->batch_boxes_cap) {
+        if (H->batch_boxes_pin) (void)hipHostFree(H->batch_boxes_pin);
+        H->batch_boxes_pin = nullptr;
+        double* old = H->batch_boxes_dev;
+        H->batch_boxes_dev = nullptr; H->batch_boxes_cap = 0;
+        dfree(H, old);
+        check_hip(hipHostMalloc((void**)&H->batch_boxes_pin, sizeof(double) * 8 * (size_t)nconf, hipHostMallocDefault),
+                  "hipHostMalloc (boxes)");
+        H->batch_boxes_dev = dalloc<double>(H, 8 * (size_t)nconf);
+        H->batch_boxes_cap = nconf;
+    }
+    for (int32_t c = 0; c < nconf; c++) {
+        const double* b = boxes_host + 9 * (size_t)c;
+        double* o = H->batch_boxes_pin + 8 * (size_t)c;
+        o[0] = b[0]; o[1] = b[4]; o[2] = b[8]; o[3] = b[3]; o[4] = b[6]; o[5] = b[7]; o[6] = 0; o[7] = 0;
+    }
+    check_hip(hipMemcpyAsync(H->batch_boxes_dev, H->batch_boxes_pin, sizeof(double) * 8 * (size_t)nconf,
+                             hipMemcpyHostToDevice, h.stream), "H2D boxes");
+    check_hip(hipEventRecord(H->batch_boxes_ev, h.stream), "hipEventRecord (boxes)");
 }
 
 static int batch_pbc_pass_size(const cf_handle* H, int nconf) {
@@ -1922,30 +1955,7 @@ CF_EXPORT int cf_compute_batch_periodic(cf_handle* H, int32_t nconf, const doubl
             double* base = dalloc<double>(H, cf::batch_pbc_doubles_per_conf(h) * (size_t)pass);
             cf::batch_pbc_carve(h, base, pass, H->batch_pbc);
         }
-        // the boxes: (Lx, Ly, Lz, bx, cx, cy, 0, 0) per conformation into the pinned copy, one upload
-        // for the whole call.  The pinned copy of the previous call is reused once its upload is done
-        // (a wait for that copy, which the stream reached before the previous call's kernels).
-        if (!H->batch_boxes_ev) check_hip(hipEventCreateWithFlags(&H->batch_boxes_ev, hipEventDisableTiming), "hipEventCreate");
-        else check_hip(hipEventSynchronize(H->batch_boxes_ev), "hipEventSynchronize (boxes)");
-        if (nconf > H->batch_boxes_cap) {
-            if (H->batch_boxes_pin) (void)hipHostFree(H->batch_boxes_pin);
-            H->batch_boxes_pin = nullptr;
-            double* old = H->batch_boxes_dev;
-            H->batch_boxes_dev = nullptr; H->batch_boxes_cap = 0;
-            dfree(H, old);
-            check_hip(hipHostMalloc((void**)&H->batch_boxes_pin, sizeof(double) * 8 * (size_t)nconf, hipHostMallocDefault),
-                      "hipHostMalloc (boxes)");
-            H->batch_boxes_dev = dalloc<double>(H, 8 * (size_t)nconf);
-            H->batch_boxes_cap = nconf;
-        }
-        for (int32_t c = 0; c < nconf; c++) {
-            const double* b = boxes_host + 9 * (size_t)c;
-            double* o = H->batch_boxes_pin + 8 * (size_t)c;
-            o[0] = b[0]; o[1] = b[4]; o[2] = b[8]; o[3] = b[3]; o[4] = b[6]; o[5] = b[7]; o[6] = 0; o[7] = 0;
-        }
-        check_hip(hipMemcpyAsync(H->batch_boxes_dev, H->batch_boxes_pin, sizeof(double) * 8 * (size_t)nconf,
-                                 hipMemcpyHostToDevice, h.stream), "H2D boxes");
-        check_hip(hipEventRecord(H->batch_boxes_ev, h.stream), "hipEventRecord (boxes)");
+        batch_boxes_upload(H, nconf, boxes_host);
         // eager launches on the handle's stream, never captured or replayed and not bracketed by the
         // per-phase timing events; the handle's k-space algorithm, precision, list and skin are not used
         const size_t n = (size_t)h.n;
@@ -2073,44 +2083,129 @@ CF_EXPORT int cf_compute_batch_vjp(cf_handle* H, int32_t nconf, const double* po
     });
 }
 
+// The host forms of the two VJP calls: positions and cotangents up through the handle's staging
+// buffer, `call(pos, e_bar, q_bar, f_bar, grad)` on the device copies, the gradients back.
+using BatchVjpCall = std::function<int(const double*, const double*, const double*, const double*, double*)>;
+static void batch_vjp_staged(cf_handle* H, int32_t nconf, const double* pos_host, const double* energy_bar_host,
+                             const double* charges_bar_host, const double* forces_bar_host, double* grad_host,
+                             const BatchVjpCall& call) {
+    cf::Handle& h = H->h;
+    check_hip(hipSetDevice(h.device), "hipSetDevice");
+    const size_t n = (size_t)h.n, B = (size_t)nconf;
+    const size_t np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+    if (nconf > H->batch_grad_stage_confs) {
+        double* old = H->batch_grad_stage;
+        H->batch_grad_stage = nullptr; H->batch_grad_stage_confs = 0;
+        dfree(H, old);
+        H->batch_grad_stage = dalloc<double>(H, B * (3 * n + 1 + n + 3 * n + np));
+        H->batch_grad_stage_confs = nconf;
+    }
+    double* pos = H->batch_grad_stage;
+    double* eb = pos + 3 * n * B;
+    double* qb = eb + B;
+    double* fb = qb + n * B;
+    double* grad = fb + 3 * n * B;
+    check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+              "H2D positions");
+    if (energy_bar_host)
+        check_hip(hipMemcpyAsync(eb, energy_bar_host, sizeof(double) * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D energy cotangent");
+    if (charges_bar_host)
+        check_hip(hipMemcpyAsync(qb, charges_bar_host, sizeof(double) * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D charge cotangent");
+    if (forces_bar_host)
+        check_hip(hipMemcpyAsync(fb, forces_bar_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D force cotangent");
+    const int rc = call(pos, energy_bar_host ? eb : nullptr, charges_bar_host ? qb : nullptr,
+                        forces_bar_host ? fb : nullptr, grad);
+    if (rc != CF_OK) throw CfError(rc, g_err);
+    check_hip(hipMemcpyAsync(grad_host, grad, sizeof(double) * np * B, hipMemcpyDeviceToHost, h.stream), "D2H grad");
+    check_hip(hipStreamSynchronize(h.stream), "sync");
+}
+
 CF_EXPORT int cf_compute_batch_vjp_host(cf_handle* H, int32_t nconf, const double* pos_host,
                                         const double* energy_bar_host, const double* charges_bar_host,
                                         const double* forces_bar_host, double* grad_host) {
     return guarded([&] {
         batch_vjp_precheck(H, nconf, pos_host, grad_host, "cf_compute_batch_vjp_host");
         if (nconf == 0) return;
+        batch_vjp_staged(H, nconf, pos_host, energy_bar_host, charges_bar_host, forces_bar_host, grad_host,
+                         [&](const double* pos, const double* eb, const double* qb, const double* fb, double* grad) {
+                             return cf_compute_batch_vjp(H, nconf, pos, eb, qb, fb, grad);
+                         });
+    });
+}
+
+// ---- parameter gradients of the periodic batch (cf_kernels_batch_pbc_grad.hip) ---------------------
+// the pass keeps the periodic forward workspace and coefd, qdot, g, a together at or below kBatchAutoBytes
+static int batch_pbc_vjp_pass_size(const cf_handle* H, int nconf) {
+    const size_t per =
+        (cf::batch_pbc_doubles_per_conf(H->h) + cf::batch_pbc_grad_doubles_per_conf(H->h)) * sizeof(double);
+    int64_t lim = H->batch_limit > 0 ? H->batch_limit : (int64_t)std::max<size_t>(1, kBatchAutoBytes / per);
+    lim = std::min<int64_t>(lim, cf::kBatchMaxPass);
+    return (int)std::min<int64_t>(lim, nconf);
+}
+
+CF_EXPORT int cf_compute_batch_periodic_vjp(cf_handle* H, int32_t nconf, const double* pos_dev,
+                                            const double* boxes_host, const double* energy_bar_dev,
+                                            const double* charges_bar_dev, const double* forces_bar_dev,
+                                            double* grad_dev) {
+    return guarded([&] {
+        if (!grad_dev) fail(CF_ERR_INVALID, "null argument");
+        batch_periodic_precheck(H, nconf, pos_dev, boxes_host, "cf_compute_batch_periodic_vjp", "cf_compute_batch_vjp");
+        if (nconf == 0) return;
         cf::Handle& h = H->h;
         check_hip(hipSetDevice(h.device), "hipSetDevice");
-        const size_t n = (size_t)h.n, B = (size_t)nconf;
-        const size_t np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
-        if (nconf > H->batch_grad_stage_confs) {
-            double* old = H->batch_grad_stage;
-            H->batch_grad_stage = nullptr; H->batch_grad_stage_confs = 0;
-            dfree(H, old);
-            H->batch_grad_stage = dalloc<double>(H, B * (3 * n + 1 + n + 3 * n + np));
-            H->batch_grad_stage_confs = nconf;
+        const size_t n = (size_t)h.n, np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        if (!energy_bar_dev && !charges_bar_dev && !forces_bar_dev) {   // zero cotangent: exact zeros, no pass
+            check_hip(hipMemsetAsync(grad_dev, 0, sizeof(double) * np * (size_t)nconf, h.stream), "memset grad");
+            return;
         }
-        double* pos = H->batch_grad_stage;
-        double* eb = pos + 3 * n * B;
-        double* qb = eb + B;
-        double* fb = qb + n * B;
-        double* grad = fb + 3 * n * B;
-        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
-                  "H2D positions");
-        if (energy_bar_host)
-            check_hip(hipMemcpyAsync(eb, energy_bar_host, sizeof(double) * B, hipMemcpyHostToDevice, h.stream),
-                      "H2D energy cotangent");
-        if (charges_bar_host)
-            check_hip(hipMemcpyAsync(qb, charges_bar_host, sizeof(double) * n * B, hipMemcpyHostToDevice, h.stream),
-                      "H2D charge cotangent");
-        if (forces_bar_host)
-            check_hip(hipMemcpyAsync(fb, forces_bar_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
-                      "H2D force cotangent");
-        const int rc = cf_compute_batch_vjp(H, nconf, pos, energy_bar_host ? eb : nullptr, charges_bar_host ? qb : nullptr,
-                                            forces_bar_host ? fb : nullptr, grad);
-        if (rc != CF_OK) throw CfError(rc, g_err);
-        check_hip(hipMemcpyAsync(grad_host, grad, sizeof(double) * np * B, hipMemcpyDeviceToHost, h.stream), "D2H grad");
-        check_hip(hipStreamSynchronize(h.stream), "sync");
+        const int pass = batch_pbc_vjp_pass_size(H, nconf);
+        if (pass > H->batch_pbc.cap) {   // first call or growth: allocates (and so synchronises)
+            double* old = H->batch_pbc.base;
+            H->batch_pbc = cf::BatchPbcWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_pbc_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_pbc_carve(h, base, pass, H->batch_pbc);
+        }
+        if (pass > H->batch_pbc_grad.cap) {
+            double* old = H->batch_pbc_grad.base;
+            H->batch_pbc_grad = cf::BatchPbcGradWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_pbc_grad_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_pbc_grad_carve(h, base, pass, H->batch_pbc_grad);
+        }
+        batch_boxes_upload(H, nconf, boxes_host);
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events (as cf_compute_batch_periodic)
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            cf::launch_batch_pbc_vjp(h, H->batch_pbc, H->batch_pbc_grad, m, pos_dev + 3 * n * c0,
+                                     H->batch_boxes_dev + 8 * (size_t)c0, energy_bar_dev ? energy_bar_dev + c0 : nullptr,
+                                     charges_bar_dev ? charges_bar_dev + n * c0 : nullptr,
+                                     forces_bar_dev ? forces_bar_dev + 3 * n * c0 : nullptr, grad_dev + np * c0);
+            H->batch_passes++;
+        }
+        launch_check(h, "compute_batch_periodic_vjp");
+    });
+}
+
+CF_EXPORT int cf_compute_batch_periodic_vjp_host(cf_handle* H, int32_t nconf, const double* pos_host,
+                                                 const double* boxes_host, const double* energy_bar_host,
+                                                 const double* charges_bar_host, const double* forces_bar_host,
+                                                 double* grad_host) {
+    return guarded([&] {
+        if (!grad_host) fail(CF_ERR_INVALID, "null argument");
+        batch_periodic_precheck(H, nconf, pos_host, boxes_host, "cf_compute_batch_periodic_vjp_host",
+                                "cf_compute_batch_vjp_host");
+        if (nconf == 0) return;
+        batch_vjp_staged(H, nconf, pos_host, energy_bar_host, charges_bar_host, forces_bar_host, grad_host,
+                         [&](const double* pos, const double* eb, const double* qb, const double* fb, double* grad) {
+                             return cf_compute_batch_periodic_vjp(H, nconf, pos, boxes_host, eb, qb, fb, grad);
+                         });
     });
 }
 

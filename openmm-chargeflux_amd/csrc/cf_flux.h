@@ -1,6 +1,7 @@
 // cf_flux.h -- the charge-flux term bodies, shared by the single-evaluation kernel k_flux_terms
 // (cf_kernels_core.hip) and the batched ones k_b_flux (cf_kernels_batch.hip) and k_bp_flux
-// (cf_kernels_batch_pbc.hip), with the other bodies the batched kernels share: one definition of the
+// (cf_kernels_batch_pbc.hip), with the other bodies the batched kernels share (the periodic ones and
+// their parameter gradients, cf_kernels_batch_pbc_grad.hip: load_box, phase): one definition of the
 // reference's formulas (ReferenceCoulKernels.cpp, RCK: bonds :42-80, angles :81-162, waters
 // :163-227), so the two paths cannot drift apart.
 #pragma once
@@ -124,6 +125,26 @@ __device__ __forceinline__ void batch_flux_block(int nconf, int n, int nterms, i
     __syncthreads();
     const int len = (int)(batch_dqdx_at(min(g0 + 256, total), nterms, nb, na, nd3) - base);
     for (int e = threadIdx.x; e < len; e += 256) dqdx_all[base + e] = st[e];
+}
+
+// the box of conformation c of a periodic batch: diagonal L and off-diagonals T = (bx, cx, cy)
+__device__ __forceinline__ void load_box(const double* __restrict__ boxes, size_t c, double3& L, double3& T) {
+    const double* b = boxes + 8 * c;
+    L = make_double3(b[0], b[1], b[2]);
+    T = make_double3(b[3], b[4], b[5]);
+}
+
+// e^{i k.r} of one atom from its table entries row[m * stride] (stride 1: the atom-major table,
+// stride N: the entry-major one): X[nx] Y[|ny|]^(sign) Z[|nz|]^(sign) (nx >= 0)
+__device__ __forceinline__ double2 phase(const double2* __restrict__ row, size_t stride, int KX, int KY, int nx,
+                                         int ny, int nz) {
+    const double2 X = row[nx * stride];
+    double2 Y = row[(KX + abs(ny)) * stride];
+    double2 Z = row[(KX + KY + abs(nz)) * stride];
+    if (ny < 0) Y.y = -Y.y;
+    if (nz < 0) Z.y = -Z.y;
+    const double ar = X.x * Y.x - X.y * Y.y, ai = X.x * Y.y + X.y * Y.x;
+    return make_double2(ar * Z.x - ai * Z.y, ar * Z.y + ai * Z.x);
 }
 
 // chain rule of atom b: (fx, fy, fz) -= sum_e dE/dq[a_e] dq_{a_e}/dx_b over the ccsr entries of b

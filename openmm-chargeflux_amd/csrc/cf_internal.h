@@ -380,6 +380,31 @@ void batch_pbc_carve(const Handle& h, double* base, int cap, BatchPbcWs& w);
 // boxes: device, [nconf][8] = (Lx, Ly, Lz, bx, cx, cy, -, -) per conformation
 void launch_batch_pbc(Handle& h, const BatchPbcWs& w, int nconf, const double* pos, const double* boxes, int flags,
                       double* forces, double* energy, double* charges);
+// its first launches, shared with the parameter gradients: k_bp_flux + k_b_charges into w (q, dq
+// slots, dq/dx), and k_bp_tables into w (both phase tables)
+void launch_batch_pbc_flux_charges(Handle& h, const BatchPbcWs& w, int nconf, const double* pos, const double* boxes,
+                                   double* charges);
+void launch_batch_pbc_tables(Handle& h, const BatchPbcWs& w, int nconf, const double* pos, const double* boxes);
+
+// parameter gradients of the periodic batch (cf_kernels_batch_pbc_grad.hip,
+// cf_compute_batch_periodic_vjp): the extra workspace of one pass beside BatchPbcWs, carved from one
+// allocation of cap * batch_pbc_grad_doubles_per_conf doubles (the double2 array first: 16-B aligned)
+struct BatchPbcGradWs {
+    double* base = nullptr;
+    int cap = 0;                // conformations the arrays hold
+    double2* coefd = nullptr;   // [cap][khalf] 2 c eak (Re Sdot, Im Sdot): the structure factor's tangent
+    double* qdot = nullptr;     // [cap][N] tangent of the charges along the force cotangent
+    double* g = nullptr;        // [cap][N] dE/dq
+    double* a = nullptr;        // [cap][N] adjoint weight e_bar g + q_bar - h
+};
+size_t batch_pbc_grad_doubles_per_conf(const Handle& h);
+void batch_pbc_grad_carve(const Handle& h, double* base, int cap, BatchPbcGradWs& w);
+// one pass of nconf <= min(w.cap, gw.cap) conformations on h.stream: at most eight launches, whatever
+// nconf.  boxes: device, [nconf][8] as launch_batch_pbc; e_bar [nconf], q_bar [nconf][N], f_bar
+// [nconf][N][3]: device or null (= zero); grad [nconf][N + 2 nb + 2 na + 5 nw] overwritten
+void launch_batch_pbc_vjp(Handle& h, const BatchPbcWs& w, const BatchPbcGradWs& gw, int nconf, const double* pos,
+                          const double* boxes, const double* e_bar, const double* q_bar, const double* f_bar,
+                          double* grad);
 
 void check_hip(hipError_t e, const char* what);
 

@@ -27,13 +27,6 @@
 
 namespace cf {
 
-// the conformation's box: diagonal L and off-diagonals T = (bx, cx, cy)
-__device__ __forceinline__ void load_box(const double* __restrict__ boxes, size_t c, double3& L, double3& T) {
-    const double* b = boxes + 8 * c;
-    L = make_double3(b[0], b[1], b[2]);
-    T = make_double3(b[3], b[4], b[5]);
-}
-
 // ---------------------------------------------------------------------------------
 // 1. flux terms: k_b_flux with the conformation's L, T and pbc = 1 (the T != 0 branch of delta_r
 //    is per conformation here: a batch may mix orthorhombic and triclinic boxes).  pbc is a kernel
@@ -84,19 +77,6 @@ __global__ void __launch_bounds__(256) k_bp_tables(long total, int n, int KX, in
     sincos((m * (2.0 * kPi / L)) * xw, &s, &co);
     tab_all[g] = make_double2(co, s);
     tab_t_all[gt] = make_double2(co, s);
-}
-
-// e^{i k.r} of one atom from its table entries row[m * stride] (stride 1: the atom-major table,
-// stride N: the entry-major one): X[nx] Y[|ny|]^(sign) Z[|nz|]^(sign) (nx >= 0)
-__device__ __forceinline__ double2 phase(const double2* __restrict__ row, size_t stride, int KX, int KY, int nx,
-                                         int ny, int nz) {
-    const double2 X = row[nx * stride];
-    double2 Y = row[(KX + abs(ny)) * stride];
-    double2 Z = row[(KX + KY + abs(nz)) * stride];
-    if (ny < 0) Y.y = -Y.y;
-    if (nz < 0) Z.y = -Z.y;
-    const double ar = X.x * Y.x - X.y * Y.y, ai = X.x * Y.y + X.y * Y.x;
-    return make_double2(ar * Z.x - ai * Z.y, ar * Z.y + ai * Z.x);
 }
 
 // ---------------------------------------------------------------------------------
@@ -354,6 +334,22 @@ void batch_pbc_carve(const Handle& h, double* base, int cap, BatchPbcWs& w) {
     w.e_atom = w.f_part + c * 3 * n;
 }
 
+void launch_batch_pbc_flux_charges(Handle& h, const BatchPbcWs& w, int nconf, const double* pos, const double* boxes,
+                                   double* charges) {
+    if (h.nterms > 0)
+        hipLaunchKernelGGL(k_bp_flux, dim3(nblk((int64_t)nconf * h.nterms, 256)), dim3(256), 0, h.stream, nconf, h.n,
+                           h.nterms, h.nb, h.na, h.nslots_dq, 3L * h.nd, h.term_idx, h.term_par, pos, boxes, h.pbc,
+                           w.dq_slot, w.dqdx);
+    launch_batch_charges(h, nconf, w.dq_slot, w.q, charges);
+}
+
+void launch_batch_pbc_tables(Handle& h, const BatchPbcWs& w, int nconf, const double* pos, const double* boxes) {
+    const int KX = h.kmax[0], KY = h.kmax[1], KZ = h.kmax[2];
+    const long total = (long)nconf * h.n * (KX + KY + KZ);
+    hipLaunchKernelGGL(k_bp_tables, dim3(nblk(total, 256)), dim3(256), 0, h.stream, total, h.n, KX, KY, KZ, pos, boxes,
+                       w.tab, w.tab_t);
+}
+
 void launch_batch_pbc(Handle& h, const BatchPbcWs& w, int nconf, const double* pos, const double* boxes, int flags,
                       double* forces, double* energy, double* charges) {
     if (nconf <= 0 || nconf > w.cap || nconf > kBatchMaxPass) throw std::invalid_argument("launch_batch_pbc: pass size");
@@ -363,15 +359,9 @@ void launch_batch_pbc(Handle& h, const BatchPbcWs& w, int nconf, const double* p
     const bool do_f = (flags & CF_INCLUDE_FORCES) && forces;
     const bool do_er = (flags & CF_INCLUDE_ENERGY) && energy;   // the reciprocal energy (the rest: whatever the flags)
     const long nd3 = 3L * h.nd;
-    if (h.nterms > 0)
-        hipLaunchKernelGGL(k_bp_flux, dim3(nblk((int64_t)nconf * h.nterms, 256)), dim3(256), 0, h.stream, nconf, n,
-                           h.nterms, h.nb, h.na, h.nslots_dq, nd3, h.term_idx, h.term_par, pos, boxes, h.pbc, w.dq_slot,
-                           w.dqdx);
-    launch_batch_charges(h, nconf, w.dq_slot, w.q, charges);
+    launch_batch_pbc_flux_charges(h, w, nconf, pos, boxes, charges);
     if (do_f || do_er) {
-        const long total = (long)nconf * n * (KX + KY + KZ);
-        hipLaunchKernelGGL(k_bp_tables, dim3(nblk(total, 256)), dim3(256), 0, h.stream, total, n, KX, KY, KZ, pos, boxes,
-                           w.tab, w.tab_t);
+        launch_batch_pbc_tables(h, w, nconf, pos, boxes);
         hipLaunchKernelGGL(k_bp_sfac, dim3(nblk(khalf, 256), nconf), dim3(256), 0, h.stream, n, KX, KY, KZ, khalf, h.ke,
                            1.0 / (h.alpha * h.alpha), boxes, w.q, w.tab, w.coef, w.ek);
     }

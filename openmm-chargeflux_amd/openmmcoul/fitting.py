@@ -1,14 +1,16 @@
 """Fitting a charge-flux model: the batched evaluation as a differentiable torch function of the
 base charges and the flux parameters.
 
-    model = BatchedChargeFlux(kernel, force)          # kernel initialised with force, non-periodic
+    model = BatchedChargeFlux(kernel, force)          # kernel initialised with force
     energies, forces, charges = model(q, bonds, angles, waters, positions)
+    energies, forces, charges = model(q, bonds, angles, waters, positions, boxes=boxes)   # periodic
     loss = ((forces - target) ** 2).mean()
     loss.backward()                                   # q.grad, bonds.grad, angles.grad, waters.grad
 
-Forward is cf_compute_batch, backward one cf_compute_batch_vjp (include/chargeflux.h): both run in
-libchargeflux_hip.so.  Gradients exist for the parameters only -- not for the positions, and not for
-the LJ sigma / epsilon, which are taken from `force` unchanged.
+Forward is cf_compute_batch, backward one cf_compute_batch_vjp (include/chargeflux.h); with boxes=,
+for a periodic kernel, cf_compute_batch_periodic and one cf_compute_batch_periodic_vjp with the same
+boxes.  All run in libchargeflux_hip.so.  Gradients exist for the parameters only -- not for the
+positions or the boxes, and not for the LJ sigma / epsilon, which are taken from `force` unchanged.
 """
 from __future__ import annotations
 
@@ -20,7 +22,7 @@ from .kernel import HipCalcCoulForceKernel
 
 class _BatchFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, charges, bonds, angles, waters, positions):
+    def forward(ctx, model, charges, bonds, angles, waters, positions, boxes):
         params = tuple(t.detach().to("cpu", torch.float64).contiguous() for t in (charges, bonds, angles, waters))
         model._load(params)
         k = model.kernel
@@ -29,11 +31,12 @@ class _BatchFn(torch.autograd.Function):
         forces = torch.zeros((nconf, n, 3), dtype=torch.float64, device=positions.device)
         q = torch.empty((nconf, n), dtype=torch.float64, device=positions.device)
         model._before()
-        k.execute_batch_device(positions, True, True, forces, energies, q)
+        k.execute_batch_device(positions, True, True, forces, energies, q, boxes=boxes)
         model._after()
         ctx.set_materialize_grads(False)   # an output the loss does not use: a None (NULL) cotangent
         ctx.model, ctx.params, ctx.loaded = model, params, model._loads
         ctx.inputs = (charges, bonds, angles, waters)
+        ctx.boxes = None if boxes is None else boxes.copy()   # the caller may change its array before backward
         ctx.save_for_backward(positions)
         return energies, forces, q
 
@@ -49,24 +52,27 @@ class _BatchFn(torch.autograd.Function):
         grad = torch.empty((positions.shape[0], sum(counts)), dtype=torch.float64, device=positions.device)
         cot = [None if t is None else t.detach().to(torch.float64).contiguous() for t in (e_bar, q_bar, f_bar)]
         model._before()
-        k.execute_batch_vjp_device(positions, grad, *cot)
+        k.execute_batch_vjp_device(positions, grad, *cot, boxes=ctx.boxes)
         model._after()
         g = k.split_gradient(grad.sum(dim=0, keepdim=True), counts)
         out = []
         for t, name, need in zip(ctx.inputs, ("charges", "bonds", "angles", "waters"), ctx.needs_input_grad[1:5]):
             out.append(g[name][0].reshape(t.shape).to(t.device) if need else None)
-        return (None, *out, None)
+        return (None, *out, None, None)
 
 
 class BatchedChargeFlux:
     """Energies, forces and charges of B conformations as a differentiable function of the
-    parameters.  kernel: a HipCalcCoulForceKernel initialised with `force` (non-periodic, one rank);
+    parameters.  kernel: a HipCalcCoulForceKernel initialised with `force` (one rank);
     force: the CoulForce whose topology, sigma and epsilon are used -- its charges and flux
     parameters are overwritten by every call.
 
-    __call__(charges (N,), bonds (nb,2), angles (na,2), waters (nw,5), positions (B,N,3)):
+    __call__(charges (N,), bonds (nb,2), angles (na,2), waters (nw,5), positions (B,N,3), boxes=None):
     float64 tensors, the parameters on any device, positions contiguous on the kernel's device and
-    not requiring grad.  Returns (energies (B,), forces (B,N,3), charges (B,N)) on that device.
+    not requiring grad.  boxes: for a periodic kernel, a float64 numpy array in host memory, (B,3,3)
+    with one box per conformation or (3,3) for all of them (execute_batch_host's); a copy is kept for
+    backward, and there are no gradients with respect to it.  Returns (energies (B,), forces (B,N,3),
+    charges (B,N)) on that device.
     The parameter rows are the cf_params rows: bonds (k, b), angles (k, theta0), waters
     (k1, k2, kub, b0, ub0).  A kernel on a stream of its own is synchronised with torch's current
     stream around each call."""
@@ -103,11 +109,13 @@ class BatchedChargeFlux:
         if self.kernel._stream:
             self.kernel.synchronize()
 
-    def __call__(self, charges, bonds, angles, waters, positions):
+    def __call__(self, charges, bonds, angles, waters, positions, boxes=None):
         for t, name in ((charges, "charges"), (bonds, "bonds"), (angles, "angles"), (waters, "waters"),
                         (positions, "positions")):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
                 raise ValueError(f"{name} must be a float64 torch tensor")
         if positions.requires_grad:
             raise ValueError("positions must not require grad: gradients with respect to positions are not computed")
-        return _BatchFn.apply(self, charges, bonds, angles, waters, positions)
+        if boxes is not None:   # before the parameters are loaded
+            self.kernel._batch_boxes(boxes, positions.shape[0])
+        return _BatchFn.apply(self, charges, bonds, angles, waters, positions, boxes)

@@ -354,7 +354,7 @@ class HipCalcCoulForceKernel:
                                                self._flags(includeForces, includeEnergy), ptr(forces),
                                                ptr(energies), ptr(charges)), self._lib)
 
-    # parameter gradients of the non-periodic batch (cf_compute_batch_vjp) --------------------------
+    # parameter gradients of the batch (cf_compute_batch_vjp; boxes=: cf_compute_batch_periodic_vjp) --
     def param_counts(self):
         """(N, 2 * bonds, 2 * angles, 5 * waters): the lengths of the four parameter groups of a
         gradient row (cf_get_param_counts); P is their sum."""
@@ -369,20 +369,28 @@ class HipCalcCoulForceKernel:
                                   or self._check_batch_array(t, name, trailing, module) != nconf):
                 raise ValueError(f"{name} must be a float64 {kind.__name__} for {nconf} conformations")
 
-    def execute_batch_vjp_host(self, positions, energy_bar=None, charges_bar=None, forces_bar=None):
+    def execute_batch_vjp_host(self, positions, energy_bar=None, charges_bar=None, forces_bar=None, *, boxes=None):
         """Gradients of L = energy_bar . E + charges_bar . q + forces_bar . F with respect to the base
         charges and the flux parameters, per conformation (cf_compute_batch_vjp_host; non-periodic
         systems).  positions (B,N,3), energy_bar (B,), charges_bar (B,N), forces_bar (B,N,3):
         C-contiguous float64 numpy arrays, a cotangent may be None (= zero).  Returns a dict:
         charges (B,N), bonds (B,nb,2) as (k, b), angles (B,na,2) as (k, theta0), waters (B,nw,5) as
-        (k1, k2, kub, b0, ub0) -- views of one (B,P) array, which is returned as flat."""
+        (k1, k2, kub, b0, ub0) -- views of one (B,P) array, which is returned as flat.
+        boxes (periodic systems, cf_compute_batch_periodic_vjp_host): as execute_batch_host --
+        float64 numpy (B,3,3), one box per conformation, or (3,3) for all of them."""
         if not isinstance(positions, np.ndarray):
             raise ValueError("positions must be a numpy array of shape (B, N, 3)")
         nconf = self._check_batch_array(positions, "positions", (self._n, 3))
         self._check_cotangents(nconf, energy_bar, charges_bar, forces_bar, np, np.ndarray)
+        b = self._batch_boxes(boxes, nconf) if boxes is not None else None
         counts = self.param_counts()
         flat = np.zeros((nconf, sum(counts)))
         opt = lambda a: _dp(a) if a is not None else None
+        if b is not None:
+            _cabi.check(self._lib.cf_compute_batch_periodic_vjp_host(
+                self._h, nconf, _dp(positions), _dp(b), opt(energy_bar), opt(charges_bar), opt(forces_bar),
+                _dp(flat)), self._lib)
+            return self.split_gradient(flat, counts)
         _cabi.check(self._lib.cf_compute_batch_vjp_host(self._h, nconf, _dp(positions), opt(energy_bar),
                                                         opt(charges_bar), opt(forces_bar), _dp(flat)), self._lib)
         return self.split_gradient(flat, counts)
@@ -397,19 +405,28 @@ class HipCalcCoulForceKernel:
                 "angles": flat[:, o2:o3].reshape(nconf, a2 // 2, 2),
                 "waters": flat[:, o3:o3 + w5].reshape(nconf, w5 // 5, 5)}
 
-    def execute_batch_vjp_device(self, positions, grad, energy_bar=None, charges_bar=None, forces_bar=None):
+    def execute_batch_vjp_device(self, positions, grad, energy_bar=None, charges_bar=None, forces_bar=None, *,
+                                 boxes=None):
         """The same on torch tensors (float64, on the kernel's device, contiguous): grad (B,P) is
-        overwritten (split_gradient gives its views).  Asynchronous on the kernel's stream."""
+        overwritten (split_gradient gives its views).  Asynchronous on the kernel's stream.
+        boxes (periodic systems, cf_compute_batch_periodic_vjp): a numpy array in HOST memory here
+        too, read during the call."""
         import torch
         if not isinstance(positions, torch.Tensor):
             raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
         nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
         self._check_cotangents(nconf, energy_bar, charges_bar, forces_bar, torch, torch.Tensor)
+        b = self._batch_boxes(boxes, nconf) if boxes is not None else None
         if not isinstance(grad, torch.Tensor):
             raise ValueError("grad must be a torch tensor of shape (B, P)")
         if self._check_batch_array(grad, "grad", (sum(self.param_counts()),), torch) != nconf:
             raise ValueError(f"grad must hold {nconf} conformations")
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if b is not None:
+            _cabi.check(self._lib.cf_compute_batch_periodic_vjp(
+                self._h, nconf, ptr(positions), _dp(b), ptr(energy_bar), ptr(charges_bar), ptr(forces_bar),
+                ptr(grad)), self._lib)
+            return
         _cabi.check(self._lib.cf_compute_batch_vjp(self._h, nconf, ptr(positions), ptr(energy_bar), ptr(charges_bar),
                                                    ptr(forces_bar), ptr(grad)), self._lib)
 
