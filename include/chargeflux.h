@@ -33,7 +33,8 @@ extern "C" {
                               cf_set_batch_limit, cf_get_batch_stats; cf_compute_batch_periodic,
                               cf_compute_batch_periodic_host; cf_get_param_counts, cf_compute_batch_vjp,
                               cf_compute_batch_vjp_host; cf_compute_batch_periodic_vjp,
-                              cf_compute_batch_periodic_vjp_host */
+                              cf_compute_batch_periodic_vjp_host; cf_compute_batch_lj_vjp,
+                              cf_compute_batch_lj_vjp_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -401,7 +402,8 @@ CF_EXPORT int cf_compute_batch_periodic_host(cf_handle* h, int32_t nconf, const 
  * ("Batched, parameter gradients").  No formula divides by a parameter: a term with
  * k = 0 is legal.
  * Periodic handles have cf_compute_batch_periodic_vjp (here: CF_ERR_INVALID, as cf_compute_batch).
- * Out of scope: gradients with respect to the LJ sigma / epsilon and to the positions.
+ * The LJ sigma / epsilon have cf_compute_batch_lj_vjp.  Out of scope: gradients with respect to the
+ * positions.
  * Errors and states as cf_compute_batch: a periodic handle CF_ERR_INVALID; world_size > 1 or a call
  * between cf_compute_begin and _end CF_ERR_STATE; NULL pos or grad, or nconf < 0, CF_ERR_INVALID;
  * nconf = 0 is a no-op; a NULL handle is rejected without touching a device.
@@ -461,11 +463,59 @@ CF_EXPORT int cf_compute_batch_periodic_vjp_host(cf_handle* h, int32_t nconf, co
                                                  const double* boxes_host, const double* energy_bar_host,
                                                  const double* charges_bar_host, const double* forces_bar_host,
                                                  double* grad_host);
+/*
+ * LJ parameter gradients of both batches: the reverse-mode product of cf_compute_batch (non-periodic
+ * handle) or cf_compute_batch_periodic (periodic handle) with respect to every atom's Lennard-Jones
+ * sigma and epsilon -- the parameters a charge-flux model is fitted together with.  One entry point
+ * serves both kinds of handle:
+ *   boxes_host      periodic handle: [nconf][9] fp64 HOST as cf_compute_batch_periodic (the same
+ *                   pinned copy, upload and reuse rule; every box checked by cf_compute's rules
+ *                   before anything is launched or counted -- a bad box gives CF_ERR_INVALID with a
+ *                   message naming the conformation index); NULL gives CF_ERR_INVALID.
+ *                   Non-periodic handle: must be NULL, anything else gives CF_ERR_INVALID
+ *   pos_dev         [nconf][N][3] fp64 DEVICE, conformation-major
+ *   energy_bar_dev  [nconf] fp64 DEVICE, or NULL (= zero)
+ *   forces_bar_dev  [nconf][N][3] fp64 DEVICE, or NULL (= zero)
+ *   grad_dev        [nconf][2 N] fp64 DEVICE, OVERWRITTEN: per conformation dL/dsigma[N], then
+ *                   dL/depsilon[N]; not summed over the conformations
+ * with L = e_bar E + sum_i F_bar_i . F_i per conformation.  There is no charge cotangent: the charges
+ * do not depend on sigma or epsilon, and neither does the pair set, so only the LJ term of E and F
+ * enters (no flux, charge or k-space stage).  With both cotangents NULL grad is set to exact zeros
+ * (one memset; the call and its conformations are counted, no pass).
+ * Closed form: the handle stores lj_i = (sigma_i / 2, 2 sqrt(eps_i)); a pair carries
+ * U_ij = e4 s6 (s6 - 1) with A = lj_i.x + lj_j.x, e4 = lj_i.y lj_j.y, s6 = (A / r)^6, over every
+ * non-excluded pair (periodic: minimum image within the cutoff).  With rdot_ij = d_ij . (F_bar_i -
+ * F_bar_j) / r:
+ *   dL/dsigma_i = 1/2 sum_j e4 (A^5 / r^6) [e_bar (12 s6 - 6) + (144 s6 - 36) rdot_ij / r]
+ *   dL/deps_i   = (2 / lj_i.y) sum_j lj_j.y [e_bar s6 (s6 - 1) + (12 s6^2 - 6 s6) rdot_ij / r]
+ * Nothing divides by sigma: sigma_i = sigma_j = 0 is legal and gives 0.
+ * CONVENTION: an atom with eps_i = 0 receives exactly 0 for dL/deps_i (and, by the formula, for
+ * dL/dsigma_i).  The true derivative of sqrt(eps_i eps_j) is singular there; such an atom has no LJ
+ * interaction, and a fit leaves it at 0.
+ * Errors and states as the other VJP calls: a NULL handle is rejected without touching a device; NULL
+ * pos or grad, or nconf < 0, CF_ERR_INVALID; world_size > 1 or a call between cf_compute_begin and
+ * _end CF_ERR_STATE; nconf = 0 is a no-op that counts nothing; a guard bit already set fails the call.
+ * Always fp64, eager launches on the handle's stream (never captured or replayed, not recorded by
+ * cf_set_timing), asynchronous.  One kernel launch per pass and no workspace; a pass is
+ * min(cf_set_batch_limit or 65535, nconf) conformations.  No atomics; every sum's order depends only
+ * on N and the topology, so a conformation's row is bitwise the same alone, at any position of any
+ * batch, under any pass size and in the host and the device form.  cf_get_batch_stats counts it;
+ * cf_compute's state and diagnostics are not touched.  It reads the LJ buffer cf_update_parameters
+ * last wrote.  No guard bits.
+ */
+CF_EXPORT int cf_compute_batch_lj_vjp(cf_handle* h, int32_t nconf, const double* pos_dev, const double* boxes_host,
+                                      const double* energy_bar_dev, const double* forces_bar_dev,
+                                      double* grad_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_lj_vjp_host(cf_handle* h, int32_t nconf, const double* pos_host,
+                                           const double* boxes_host, const double* energy_bar_host,
+                                           const double* forces_bar_host, double* grad_host);
 /* cap on the conformations evaluated per pass (bounds the batch workspace); 0 = automatic: as many
  * as keep the workspace (per conformation q[N], the flux slots, dq/dx, dE/dq[N], F[3N], e[N]; a
  * periodic batch also the phase tables, 4 doubles per [N][kmax_x + kmax_y + kmax_z] entry, and 3
  * doubles per k-vector; cf_compute_batch_vjp also qdot[N], g[N], a[N]; cf_compute_batch_periodic_vjp
- * those three and 2 more doubles per k-vector) at or below 256 MiB, and never more than 65535.  A
+ * those three and 2 more doubles per k-vector) at or below 256 MiB, and never more than 65535
+ * (cf_compute_batch_lj_vjp has no workspace: automatic is 65535).  A
  * larger batch runs as consecutive passes.  Applies to every batch form; cf_get_batch_stats counts
  * them all (a VJP call with all cotangents NULL counts its call and conformations, and no pass). */
 CF_EXPORT int cf_set_batch_limit(cf_handle* h, int32_t max_conformations);

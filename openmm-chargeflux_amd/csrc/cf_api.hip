@@ -82,6 +82,10 @@ struct cf_handle {
     // cf_compute_batch_periodic_vjp: the extra workspace beside `batch_pbc` (the second coefficient
     // array, qdot, g, a), in H->allocs; its host form stages through batch_grad_stage
     cf::BatchPbcGradWs batch_pbc_grad;
+    // cf_compute_batch_lj_vjp needs no workspace; its host form stages through batch_lj_stage
+    // (positions, both cotangents, the [2N] gradient rows), in H->allocs
+    double* batch_lj_stage = nullptr;
+    int64_t batch_lj_stage_confs = 0;
 };
 
 namespace {
@@ -2206,6 +2210,98 @@ CF_EXPORT int cf_compute_batch_periodic_vjp_host(cf_handle* H, int32_t nconf, co
                          [&](const double* pos, const double* eb, const double* qb, const double* fb, double* grad) {
                              return cf_compute_batch_periodic_vjp(H, nconf, pos, boxes_host, eb, qb, fb, grad);
                          });
+    });
+}
+
+// ---- LJ sigma / epsilon gradients of both batches (cf_kernels_batch_lj_grad.hip) --------------------
+// Everything that can refuse the call, before anything is launched, staged or counted: the rules of
+// the handle's own batch (batch_periodic_precheck with every box, or no boxes at all).
+static void batch_lj_vjp_precheck(cf_handle* H, int32_t nconf, const double* pos, const double* boxes_host,
+                                  const double* grad, const char* name) {
+    if (!H || !pos || !grad) fail(CF_ERR_INVALID, "null argument");
+    if (H->h.pbc) {
+        if (!boxes_host) fail(CF_ERR_INVALID, std::string(name) + ": a periodic handle needs boxes_host (null argument)");
+        batch_periodic_precheck(H, nconf, pos, boxes_host, name);
+        return;
+    }
+    if (nconf < 0) fail(CF_ERR_INVALID, "nconf must be >= 0");
+    cf::Handle& h = H->h;
+    if (h.world > 1) fail(CF_ERR_STATE, std::string(name) + " is single-rank only");
+    if (h.pending_flags >= 0) fail(CF_ERR_STATE, std::string(name) + " during a begun evaluation");
+    if (boxes_host) fail(CF_ERR_INVALID, std::string(name) + ": this handle is not periodic (boxes_host must be NULL)");
+    guard_check(h);
+}
+
+// no workspace: the pass size is the caller's limit or the grid's
+static int batch_lj_pass_size(const cf_handle* H, int nconf) {
+    const int64_t lim = H->batch_limit > 0 ? std::min<int64_t>(H->batch_limit, cf::kBatchMaxPass) : cf::kBatchMaxPass;
+    return (int)std::min<int64_t>(lim, nconf);
+}
+
+CF_EXPORT int cf_compute_batch_lj_vjp(cf_handle* H, int32_t nconf, const double* pos_dev, const double* boxes_host,
+                                      const double* energy_bar_dev, const double* forces_bar_dev, double* grad_dev) {
+    return guarded([&] {
+        batch_lj_vjp_precheck(H, nconf, pos_dev, boxes_host, grad_dev, "cf_compute_batch_lj_vjp");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n;
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        if (!energy_bar_dev && !forces_bar_dev) {   // zero cotangent: exact zeros, no pass
+            check_hip(hipMemsetAsync(grad_dev, 0, sizeof(double) * 2 * n * (size_t)nconf, h.stream), "memset grad");
+            return;
+        }
+        if (h.pbc) batch_boxes_upload(H, nconf, boxes_host);
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events (as cf_compute_batch); one launch per pass
+        const int pass = batch_lj_pass_size(H, nconf);
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            cf::launch_batch_lj_vjp(h, m, pos_dev + 3 * n * c0, h.pbc ? H->batch_boxes_dev + 8 * (size_t)c0 : nullptr,
+                                    energy_bar_dev ? energy_bar_dev + c0 : nullptr,
+                                    forces_bar_dev ? forces_bar_dev + 3 * n * c0 : nullptr, grad_dev + 2 * n * c0);
+            H->batch_passes++;
+        }
+        launch_check(h, "compute_batch_lj_vjp");
+    });
+}
+
+// synchronous host form: positions and cotangents up through a staging buffer of the handle, the
+// gradients back
+CF_EXPORT int cf_compute_batch_lj_vjp_host(cf_handle* H, int32_t nconf, const double* pos_host,
+                                           const double* boxes_host, const double* energy_bar_host,
+                                           const double* forces_bar_host, double* grad_host) {
+    return guarded([&] {
+        batch_lj_vjp_precheck(H, nconf, pos_host, boxes_host, grad_host, "cf_compute_batch_lj_vjp_host");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, B = (size_t)nconf;
+        if (nconf > H->batch_lj_stage_confs) {
+            double* old = H->batch_lj_stage;
+            H->batch_lj_stage = nullptr; H->batch_lj_stage_confs = 0;
+            dfree(H, old);
+            H->batch_lj_stage = dalloc<double>(H, B * (3 * n + 1 + 3 * n + 2 * n));
+            H->batch_lj_stage_confs = nconf;
+        }
+        double* pos = H->batch_lj_stage;
+        double* eb = pos + 3 * n * B;
+        double* fb = eb + B;
+        double* grad = fb + 3 * n * B;
+        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D positions");
+        if (energy_bar_host)
+            check_hip(hipMemcpyAsync(eb, energy_bar_host, sizeof(double) * B, hipMemcpyHostToDevice, h.stream),
+                      "H2D energy cotangent");
+        if (forces_bar_host)
+            check_hip(hipMemcpyAsync(fb, forces_bar_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                      "H2D force cotangent");
+        const int rc = cf_compute_batch_lj_vjp(H, nconf, pos, boxes_host, energy_bar_host ? eb : nullptr,
+                                               forces_bar_host ? fb : nullptr, grad);
+        if (rc != CF_OK) throw CfError(rc, g_err);
+        check_hip(hipMemcpyAsync(grad_host, grad, sizeof(double) * 2 * n * B, hipMemcpyDeviceToHost, h.stream), "D2H grad");
+        check_hip(hipStreamSynchronize(h.stream), "sync");
     });
 }
 

@@ -406,6 +406,13 @@ void launch_batch_pbc_vjp(Handle& h, const BatchPbcWs& w, const BatchPbcGradWs& 
                           const double* boxes, const double* e_bar, const double* q_bar, const double* f_bar,
                           double* grad);
 
+// LJ sigma / epsilon gradients of both batches (cf_kernels_batch_lj_grad.hip, cf_compute_batch_lj_vjp):
+// one pass of nconf <= kBatchMaxPass conformations on h.stream, one launch, no workspace.  boxes:
+// device, [nconf][8] as launch_batch_pbc on a periodic handle, null on a non-periodic one; e_bar
+// [nconf], f_bar [nconf][N][3]: device or null (= zero); grad [nconf][2 N] overwritten
+void launch_batch_lj_vjp(Handle& h, int nconf, const double* pos, const double* boxes, const double* e_bar,
+                         const double* f_bar, double* grad);
+
 void check_hip(hipError_t e, const char* what);
 
 // ---- fp64 math helpers shared by the pair and grid kernels -------------------------

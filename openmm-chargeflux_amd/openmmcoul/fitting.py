@@ -1,5 +1,5 @@
 """Fitting a charge-flux model: the batched evaluation as a differentiable torch function of the
-base charges and the flux parameters.
+base charges, the flux parameters and, optionally, the LJ sigma / epsilon.
 
     model = BatchedChargeFlux(kernel, force)          # kernel initialised with force
     energies, forces, charges = model(q, bonds, angles, waters, positions)
@@ -7,10 +7,21 @@ base charges and the flux parameters.
     loss = ((forces - target) ** 2).mean()
     loss.backward()                                   # q.grad, bonds.grad, angles.grad, waters.grad
 
+    sigmas, epsilons = model.lj_parameters()          # fitted together with the LJ parameters
+    energies, forces, charges = model(q, bonds, angles, waters, positions, sigmas=sigmas, epsilons=epsilons)
+    loss.backward()                                   # ... and sigmas.grad, epsilons.grad
+
 Forward is cf_compute_batch, backward one cf_compute_batch_vjp (include/chargeflux.h); with boxes=,
 for a periodic kernel, cf_compute_batch_periodic and one cf_compute_batch_periodic_vjp with the same
-boxes.  All run in libchargeflux_hip.so.  Gradients exist for the parameters only -- not for the
-positions or the boxes, and not for the LJ sigma / epsilon, which are taken from `force` unchanged.
+boxes.  With sigmas= and epsilons= backward adds one cf_compute_batch_lj_vjp (either kind of kernel,
+the same boxes) if one of the two requires grad, and skips the other VJP call when none of its four
+inputs does.  Without them the LJ parameters are taken from `force` unchanged and the path is the
+one above: no extra call.  All run in libchargeflux_hip.so.  Gradients exist for the parameters
+only -- not for the positions or the boxes.
+
+Convention (cf_compute_batch_lj_vjp): an atom with epsilon = 0 receives exactly 0 for its sigma and
+epsilon gradients.  The true derivative of sqrt(eps_i eps_j) is singular there; such an atom has no
+LJ interaction, and an optimiser leaves it at 0.
 """
 from __future__ import annotations
 
@@ -22,8 +33,9 @@ from .kernel import HipCalcCoulForceKernel
 
 class _BatchFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, charges, bonds, angles, waters, positions, boxes):
-        params = tuple(t.detach().to("cpu", torch.float64).contiguous() for t in (charges, bonds, angles, waters))
+    def forward(ctx, model, charges, bonds, angles, waters, sigmas, epsilons, positions, boxes):
+        given = (charges, bonds, angles, waters) + (() if sigmas is None else (sigmas, epsilons))
+        params = tuple(t.detach().to("cpu", torch.float64).contiguous() for t in given)
         model._load(params)
         k = model.kernel
         nconf, n = positions.shape[0], positions.shape[1]
@@ -36,6 +48,7 @@ class _BatchFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)   # an output the loss does not use: a None (NULL) cotangent
         ctx.model, ctx.params, ctx.loaded = model, params, model._loads
         ctx.inputs = (charges, bonds, angles, waters)
+        ctx.lj = None if sigmas is None else (sigmas, epsilons)
         ctx.boxes = None if boxes is None else boxes.copy()   # the caller may change its array before backward
         ctx.save_for_backward(positions)
         return energies, forces, q
@@ -48,34 +61,50 @@ class _BatchFn(torch.autograd.Function):
         if model._loads != ctx.loaded:   # another forward has changed the parameters since: put these back
             model._load(ctx.params)
             ctx.loaded = model._loads
-        counts = k.param_counts()
-        grad = torch.empty((positions.shape[0], sum(counts)), dtype=torch.float64, device=positions.device)
+        nconf, n = positions.shape[0], positions.shape[1]
         cot = [None if t is None else t.detach().to(torch.float64).contiguous() for t in (e_bar, q_bar, f_bar)]
-        model._before()
-        k.execute_batch_vjp_device(positions, grad, *cot, boxes=ctx.boxes)
-        model._after()
-        g = k.split_gradient(grad.sum(dim=0, keepdim=True), counts)
-        out = []
-        for t, name, need in zip(ctx.inputs, ("charges", "bonds", "angles", "waters"), ctx.needs_input_grad[1:5]):
-            out.append(g[name][0].reshape(t.shape).to(t.device) if need else None)
-        return (None, *out, None, None)
+        out = [None] * 4
+        if any(ctx.needs_input_grad[1:5]):
+            counts = k.param_counts()
+            grad = torch.empty((nconf, sum(counts)), dtype=torch.float64, device=positions.device)
+            model._before()
+            k.execute_batch_vjp_device(positions, grad, *cot, boxes=ctx.boxes)
+            model._after()
+            g = k.split_gradient(grad.sum(dim=0, keepdim=True), counts)
+            for slot, (t, name, need) in enumerate(zip(ctx.inputs, ("charges", "bonds", "angles", "waters"),
+                                                       ctx.needs_input_grad[1:5])):
+                out[slot] = g[name][0].reshape(t.shape).to(t.device) if need else None
+        lj = [None, None]
+        if ctx.lj is not None and any(ctx.needs_input_grad[5:7]):
+            grad = torch.empty((nconf, 2 * n), dtype=torch.float64, device=positions.device)
+            model._before()
+            k.execute_batch_lj_vjp_device(positions, grad, cot[0], cot[2], boxes=ctx.boxes)
+            model._after()
+            g = grad.sum(dim=0)
+            for slot, (t, need) in enumerate(zip(ctx.lj, ctx.needs_input_grad[5:7])):
+                lj[slot] = g[slot * n:(slot + 1) * n].reshape(t.shape).to(t.device) if need else None
+        return (None, *out, *lj, None, None)
 
 
 class BatchedChargeFlux:
     """Energies, forces and charges of B conformations as a differentiable function of the
     parameters.  kernel: a HipCalcCoulForceKernel initialised with `force` (one rank);
     force: the CoulForce whose topology, sigma and epsilon are used -- its charges and flux
-    parameters are overwritten by every call.
+    parameters are overwritten by every call, its sigma and epsilon by a call with sigmas= and
+    epsilons= (and stay as that call left them).
 
-    __call__(charges (N,), bonds (nb,2), angles (na,2), waters (nw,5), positions (B,N,3), boxes=None):
+    __call__(charges (N,), bonds (nb,2), angles (na,2), waters (nw,5), positions (B,N,3), boxes=None,
+    *, sigmas=None, epsilons=None):
     float64 tensors, the parameters on any device, positions contiguous on the kernel's device and
     not requiring grad.  boxes: for a periodic kernel, a float64 numpy array in host memory, (B,3,3)
     with one box per conformation or (3,3) for all of them (execute_batch_host's); a copy is kept for
     backward, and there are no gradients with respect to it.  Returns (energies (B,), forces (B,N,3),
     charges (B,N)) on that device.
     The parameter rows are the cf_params rows: bonds (k, b), angles (k, theta0), waters
-    (k1, k2, kub, b0, ub0).  A kernel on a stream of its own is synchronised with torch's current
-    stream around each call."""
+    (k1, k2, kub, b0, ub0).  sigmas, epsilons: float64 (N,) tensors (nm, kJ/mol), both or neither
+    (ValueError otherwise); given, they replace the force's LJ parameters and receive gradients (an
+    atom with epsilon = 0: exactly 0 for both, the convention of cf_compute_batch_lj_vjp).  A kernel
+    on a stream of its own is synchronised with torch's current stream around each call."""
 
     def __init__(self, kernel: HipCalcCoulForceKernel, force: CoulForce):
         self.kernel, self.force = kernel, force
@@ -87,8 +116,14 @@ class BatchedChargeFlux:
         return tuple(torch.tensor(a[key], dtype=torch.float64, device=device, requires_grad=True)
                      for key in ("charges", "fbond_par", "fangle_par", "fwater_par"))
 
+    def lj_parameters(self, device=None):
+        """The force's current LJ (sigmas, epsilons) as two leaf tensors (requires_grad) on `device`."""
+        a = self.force.arrays()
+        return tuple(torch.tensor(a[key], dtype=torch.float64, device=device, requires_grad=True)
+                     for key in ("sigmas", "epsilons"))
+
     def _load(self, params):
-        q, bonds, angles, waters = (p.numpy() for p in params)
+        q, bonds, angles, waters = (p.numpy() for p in params[:4])
         f = self.force
         shapes = ((f.getNumParticles(),), (f.getNumFluxBonds(), 2), (f.getNumFluxAngles(), 2), (f.getNumFluxWaters(), 5))
         for p, name, shape in zip((q, bonds, angles, waters), ("charges", "bonds", "angles", "waters"), shapes):
@@ -98,6 +133,12 @@ class BatchedChargeFlux:
         f._fbond_par = [tuple(float(v) for v in row) for row in bonds]
         f._fangle_par = [tuple(float(v) for v in row) for row in angles]
         f._fwater_par = [tuple(float(v) for v in row) for row in waters]
+        if len(params) > 4:
+            for p, name in zip(params[4:], ("sigmas", "epsilons")):
+                if tuple(p.shape) != shapes[0]:
+                    raise ValueError(f"{name} must have shape {shapes[0]}, got {tuple(p.shape)}")
+            f._sigma = [float(v) for v in params[4].numpy()]
+            f._eps = [float(v) for v in params[5].numpy()]
         self.kernel.copyParametersToContext(f)
         self._loads += 1
 
@@ -109,13 +150,16 @@ class BatchedChargeFlux:
         if self.kernel._stream:
             self.kernel.synchronize()
 
-    def __call__(self, charges, bonds, angles, waters, positions, boxes=None):
+    def __call__(self, charges, bonds, angles, waters, positions, boxes=None, *, sigmas=None, epsilons=None):
+        if (sigmas is None) != (epsilons is None):
+            raise ValueError("sigmas and epsilons must be given together, or neither")
+        lj = () if sigmas is None else ((sigmas, "sigmas"), (epsilons, "epsilons"))
         for t, name in ((charges, "charges"), (bonds, "bonds"), (angles, "angles"), (waters, "waters"),
-                        (positions, "positions")):
+                        (positions, "positions")) + lj:
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
                 raise ValueError(f"{name} must be a float64 torch tensor")
         if positions.requires_grad:
             raise ValueError("positions must not require grad: gradients with respect to positions are not computed")
         if boxes is not None:   # before the parameters are loaded
             self.kernel._batch_boxes(boxes, positions.shape[0])
-        return _BatchFn.apply(self, charges, bonds, angles, waters, positions, boxes)
+        return _BatchFn.apply(self, charges, bonds, angles, waters, sigmas, epsilons, positions, boxes)

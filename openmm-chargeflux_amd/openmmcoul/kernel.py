@@ -430,6 +430,44 @@ class HipCalcCoulForceKernel:
         _cabi.check(self._lib.cf_compute_batch_vjp(self._h, nconf, ptr(positions), ptr(energy_bar), ptr(charges_bar),
                                                    ptr(forces_bar), ptr(grad)), self._lib)
 
+    # LJ sigma / epsilon gradients of both batches (cf_compute_batch_lj_vjp) ---------------------------
+    def execute_batch_lj_vjp_host(self, positions, energy_bar=None, forces_bar=None, *, boxes=None):
+        """Gradients of L = energy_bar . E + forces_bar . F with respect to every atom's LJ sigma and
+        epsilon, per conformation (cf_compute_batch_lj_vjp_host).  positions (B,N,3), energy_bar
+        (B,), forces_bar (B,N,3): C-contiguous float64 numpy arrays, a cotangent may be None
+        (= zero).  Returns a dict: sigmas (B,N), epsilons (B,N) -- views of one (B,2N) array, which
+        is returned as flat.  An atom with epsilon = 0 receives exactly 0 for both.
+        boxes: required for a periodic system, as execute_batch_host -- float64 numpy (B,3,3), one
+        box per conformation, or (3,3) for all of them; None for a non-periodic one."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        self._check_cotangents(nconf, energy_bar, None, forces_bar, np, np.ndarray)
+        b = self._batch_boxes(boxes, nconf) if boxes is not None else None
+        flat = np.zeros((nconf, 2 * self._n))
+        opt = lambda a: _dp(a) if a is not None else None
+        _cabi.check(self._lib.cf_compute_batch_lj_vjp_host(self._h, nconf, _dp(positions), opt(b), opt(energy_bar),
+                                                           opt(forces_bar), _dp(flat)), self._lib)
+        return {"flat": flat, "sigmas": flat[:, :self._n], "epsilons": flat[:, self._n:]}
+
+    def execute_batch_lj_vjp_device(self, positions, grad, energy_bar=None, forces_bar=None, *, boxes=None):
+        """The same on torch tensors (float64, on the kernel's device, contiguous): grad (B,2N) is
+        overwritten, sigmas then epsilons per conformation.  Asynchronous on the kernel's stream.
+        boxes: a numpy array in HOST memory here too, read during the call."""
+        import torch
+        if not isinstance(positions, torch.Tensor):
+            raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
+        self._check_cotangents(nconf, energy_bar, None, forces_bar, torch, torch.Tensor)
+        b = self._batch_boxes(boxes, nconf) if boxes is not None else None
+        if not isinstance(grad, torch.Tensor):
+            raise ValueError("grad must be a torch tensor of shape (B, 2 N)")
+        if self._check_batch_array(grad, "grad", (2 * self._n,), torch) != nconf:
+            raise ValueError(f"grad must hold {nconf} conformations")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _cabi.check(self._lib.cf_compute_batch_lj_vjp(self._h, nconf, ptr(positions), _dp(b) if b is not None else None,
+                                                      ptr(energy_bar), ptr(forces_bar), ptr(grad)), self._lib)
+
     def set_batch_limit(self, n: int):
         """Conformations evaluated per pass of a batch (bounds the batch workspace); 0 = automatic
         (a 256 MiB workspace).  Results do not depend on it."""
