@@ -34,7 +34,9 @@ extern "C" {
                               cf_compute_batch_periodic_host; cf_get_param_counts, cf_compute_batch_vjp,
                               cf_compute_batch_vjp_host; cf_compute_batch_periodic_vjp,
                               cf_compute_batch_periodic_vjp_host; cf_compute_batch_lj_vjp,
-                              cf_compute_batch_lj_vjp_host */
+                              cf_compute_batch_lj_vjp_host; cf_compute_batch_dipole,
+                              cf_compute_batch_dipole_host, cf_compute_batch_dipole_vjp,
+                              cf_compute_batch_dipole_vjp_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -510,12 +512,73 @@ CF_EXPORT int cf_compute_batch_lj_vjp(cf_handle* h, int32_t nconf, const double*
 CF_EXPORT int cf_compute_batch_lj_vjp_host(cf_handle* h, int32_t nconf, const double* pos_host,
                                            const double* boxes_host, const double* energy_bar_host,
                                            const double* forces_bar_host, double* grad_host);
+/*
+ * Dipoles and atomic polar tensors (APT) of the non-periodic batch -- what a fit to dipole surfaces
+ * and IR intensities targets.  Per conformation, with q the charges after flux (exactly
+ * cf_compute_batch's charges, to the bit):
+ *   mu[al]        = sum_a q_a x_a[al]                          (e nm)
+ *   P[b][al][be]  = d mu[al] / d x_b[be]
+ *                 = q_b delta(al, be) + sum_a x_a[al] dq_a/dx_b[be]            (e)
+ * The origin is the coordinate origin: the dipole of a charged system moves with a translation d by
+ * (sum_a q_a) d; P does not.  sum_b P_b = (sum_a q_a) I.
+ *   pos_dev      [nconf][N][3] fp64 DEVICE, conformation-major
+ *   dipole_dev   [nconf][3] fp64 DEVICE, or NULL
+ *   apt_dev      [nconf][N][3][3] fp64 DEVICE indexed [b][al][be] as above, or NULL
+ *   charges_dev  [nconf][N] fp64 DEVICE, or NULL
+ * All outputs are OVERWRITTEN.  With all three NULL the call and its conformations are counted and
+ * nothing is launched.  A pass is at most three kernel launches whatever nconf (flux terms, charges,
+ * one kernel for mu and P), in the batch workspace of cf_compute_batch with its pass size.  The
+ * charge-flux part of P is gathered over atom b's chain-rule entries in the order of the force's
+ * chain rule; no atomics, every sum's order depends only on N and the topology, so a conformation's
+ * results are bitwise the same alone, at any position of any batch, under any pass size and in the
+ * host and the device form.
+ *
+ * cf_compute_batch_dipole_vjp: the reverse-mode product with respect to the base charges and the
+ * flux parameters.  Per conformation, with cotangents mu_bar[3] and P_bar[N][3][3], the scalar is
+ * L = mu_bar . mu + sum_b P_bar_b : P_b.
+ *   dipole_bar_dev  [nconf][3] fp64 DEVICE, or NULL (= zero)
+ *   apt_bar_dev     [nconf][N][3][3] fp64 DEVICE, or NULL (= zero)
+ *   grad_dev        [nconf][P] fp64 DEVICE, OVERWRITTEN: rows in the order of cf_get_param_counts, as
+ *                   cf_compute_batch_vjp; not summed over the conformations
+ * With both cotangents NULL grad is set to exact zeros (one memset; the call and its conformations
+ * are counted, no pass).
+ * Closed form: every flux term is a sum of pieces q_a += c_a k (g(x) - ref) over its atoms (bond:
+ * g = r, c = (1, -1); angle: g = theta, c = (1, -2, 1); water: r12, r13 and r23 with the signs of its
+ * three charge slots).  With a_i = mu_bar . x_i + tr P_bar_i and w = sum_a c_a x_a:
+ *   dL/d(base charge i) = a_i
+ *   dL/dk   += (sum_a c_a a_a) (g - ref) + sum_b w^T P_bar_b grad_b g
+ *   dL/dref += -k sum_a c_a a_a
+ * Nothing divides by a parameter: a term with k = 0 is legal.  There is no pair sum and no workspace:
+ * at most two kernel launches per pass; a pass is min(cf_set_batch_limit or 65535, nconf)
+ * conformations.  The same bitwise guarantees as the forward call.
+ *
+ * Errors and states of both as cf_compute_batch_vjp: a periodic handle CF_ERR_INVALID (the dipole of
+ * a periodic cell is not defined); world_size > 1 or a call between cf_compute_begin and _end
+ * CF_ERR_STATE; NULL pos, NULL grad or nconf < 0 CF_ERR_INVALID; nconf = 0 is a no-op that counts
+ * nothing; a NULL handle is rejected without touching a device; a guard bit already set fails the
+ * call.  Always fp64, eager launches on the handle's stream (never captured or replayed, not recorded
+ * by cf_set_timing), asynchronous: inputs and outputs must stay valid until the stream reaches them.
+ * cf_get_batch_stats counts both; cf_compute's state and diagnostics are not touched; both read the
+ * parameter buffers cf_update_parameters last wrote.  No guard bits.  Out of scope: periodic handles,
+ * gradients with respect to the positions.
+ */
+CF_EXPORT int cf_compute_batch_dipole(cf_handle* h, int32_t nconf, const double* pos_dev, double* dipole_dev,
+                                      double* apt_dev, double* charges_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_dipole_host(cf_handle* h, int32_t nconf, const double* pos_host, double* dipole_host,
+                                           double* apt_host, double* charges_host);
+CF_EXPORT int cf_compute_batch_dipole_vjp(cf_handle* h, int32_t nconf, const double* pos_dev,
+                                          const double* dipole_bar_dev, const double* apt_bar_dev, double* grad_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_dipole_vjp_host(cf_handle* h, int32_t nconf, const double* pos_host,
+                                               const double* dipole_bar_host, const double* apt_bar_host,
+                                               double* grad_host);
 /* cap on the conformations evaluated per pass (bounds the batch workspace); 0 = automatic: as many
  * as keep the workspace (per conformation q[N], the flux slots, dq/dx, dE/dq[N], F[3N], e[N]; a
  * periodic batch also the phase tables, 4 doubles per [N][kmax_x + kmax_y + kmax_z] entry, and 3
  * doubles per k-vector; cf_compute_batch_vjp also qdot[N], g[N], a[N]; cf_compute_batch_periodic_vjp
  * those three and 2 more doubles per k-vector) at or below 256 MiB, and never more than 65535
- * (cf_compute_batch_lj_vjp has no workspace: automatic is 65535).  A
+ * (cf_compute_batch_lj_vjp and cf_compute_batch_dipole_vjp have no workspace: automatic is 65535).  A
  * larger batch runs as consecutive passes.  Applies to every batch form; cf_get_batch_stats counts
  * them all (a VJP call with all cotangents NULL counts its call and conformations, and no pass). */
 CF_EXPORT int cf_set_batch_limit(cf_handle* h, int32_t max_conformations);

@@ -86,6 +86,10 @@ struct cf_handle {
     // (positions, both cotangents, the [2N] gradient rows), in H->allocs
     double* batch_lj_stage = nullptr;
     int64_t batch_lj_stage_confs = 0;
+    // cf_compute_batch_dipole uses `batch`, its VJP no workspace; both host forms stage through
+    // batch_dipole_stage (in H->allocs)
+    double* batch_dipole_stage = nullptr;
+    int64_t batch_dipole_stage_confs = 0;
 };
 
 namespace {
@@ -2301,6 +2305,152 @@ CF_EXPORT int cf_compute_batch_lj_vjp_host(cf_handle* H, int32_t nconf, const do
                                                forces_bar_host ? fb : nullptr, grad);
         if (rc != CF_OK) throw CfError(rc, g_err);
         check_hip(hipMemcpyAsync(grad_host, grad, sizeof(double) * 2 * n * B, hipMemcpyDeviceToHost, h.stream), "D2H grad");
+        check_hip(hipStreamSynchronize(h.stream), "sync");
+    });
+}
+
+// ---- dipoles and atomic polar tensors of the non-periodic batch (cf_kernels_batch_dipole.hip) -------
+// The staging buffer of both host forms: positions, [3] and [N][3][3] (outputs or cotangents), and a
+// row of P >= N doubles (the charges or the gradient) per conformation.
+// Everything that can refuse the forward call, before anything is launched, staged or counted: the
+// rules of batch_vjp_precheck without a grad (every output may be NULL).
+static void batch_dipole_precheck(cf_handle* H, int32_t nconf, const double* pos, const char* name) {
+    if (!H || !pos) fail(CF_ERR_INVALID, "null argument");
+    if (nconf < 0) fail(CF_ERR_INVALID, "nconf must be >= 0");
+    cf::Handle& h = H->h;
+    if (h.world > 1) fail(CF_ERR_STATE, std::string(name) + " is single-rank only");
+    if (h.pbc) fail(CF_ERR_INVALID, std::string(name) + ": batches are non-periodic only (this handle is periodic)");
+    if (h.pending_flags >= 0) fail(CF_ERR_STATE, std::string(name) + " during a begun evaluation");
+    guard_check(h);
+}
+
+static double* batch_dipole_stage(cf_handle* H, int32_t nconf, size_t np) {
+    const size_t n = (size_t)H->h.n, B = (size_t)nconf;
+    if (nconf > H->batch_dipole_stage_confs) {
+        double* old = H->batch_dipole_stage;
+        H->batch_dipole_stage = nullptr; H->batch_dipole_stage_confs = 0;
+        dfree(H, old);
+        H->batch_dipole_stage = dalloc<double>(H, B * (3 * n + 3 + 9 * n + np));
+        H->batch_dipole_stage_confs = nconf;
+    }
+    return H->batch_dipole_stage;
+}
+
+CF_EXPORT int cf_compute_batch_dipole(cf_handle* H, int32_t nconf, const double* pos_dev, double* dipole_dev,
+                                      double* apt_dev, double* charges_dev) {
+    return guarded([&] {
+        batch_dipole_precheck(H, nconf, pos_dev, "cf_compute_batch_dipole");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        if (!dipole_dev && !apt_dev && !charges_dev) return;   // nothing asked for: counted, nothing launched
+        const int pass = batch_pass_size(H, nconf);
+        if (pass > H->batch.cap) {   // first call or growth: allocates (and so synchronises)
+            double* old = H->batch.base;
+            H->batch = cf::BatchWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_carve(h, base, pass, H->batch);
+        }
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events (as cf_compute_batch)
+        const size_t n = (size_t)h.n;
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            cf::launch_batch_dipole(h, H->batch, m, pos_dev + 3 * n * c0, dipole_dev ? dipole_dev + 3 * (size_t)c0 : nullptr,
+                                    apt_dev ? apt_dev + 9 * n * c0 : nullptr, charges_dev ? charges_dev + n * c0 : nullptr);
+            H->batch_passes++;
+        }
+        launch_check(h, "compute_batch_dipole");
+    });
+}
+
+// synchronous host form: positions up through a staging buffer of the handle, the outputs back
+CF_EXPORT int cf_compute_batch_dipole_host(cf_handle* H, int32_t nconf, const double* pos_host, double* dipole_host,
+                                           double* apt_host, double* charges_host) {
+    return guarded([&] {
+        batch_dipole_precheck(H, nconf, pos_host, "cf_compute_batch_dipole_host");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, B = (size_t)nconf;
+        double* pos = batch_dipole_stage(H, nconf, n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw);
+        double* dip = pos + 3 * n * B;
+        double* apt = dip + 3 * B;
+        double* chg = apt + 9 * n * B;
+        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D positions");
+        const int rc = cf_compute_batch_dipole(H, nconf, pos, dipole_host ? dip : nullptr, apt_host ? apt : nullptr,
+                                               charges_host ? chg : nullptr);
+        if (rc != CF_OK) throw CfError(rc, g_err);
+        if (dipole_host)
+            check_hip(hipMemcpyAsync(dipole_host, dip, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, h.stream), "D2H dipoles");
+        if (apt_host)
+            check_hip(hipMemcpyAsync(apt_host, apt, sizeof(double) * 9 * n * B, hipMemcpyDeviceToHost, h.stream),
+                      "D2H polar tensors");
+        if (charges_host)
+            check_hip(hipMemcpyAsync(charges_host, chg, sizeof(double) * n * B, hipMemcpyDeviceToHost, h.stream),
+                      "D2H charges");
+        check_hip(hipStreamSynchronize(h.stream), "sync");
+    });
+}
+
+CF_EXPORT int cf_compute_batch_dipole_vjp(cf_handle* H, int32_t nconf, const double* pos_dev,
+                                          const double* dipole_bar_dev, const double* apt_bar_dev, double* grad_dev) {
+    return guarded([&] {
+        batch_vjp_precheck(H, nconf, pos_dev, grad_dev, "cf_compute_batch_dipole_vjp");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        if (!dipole_bar_dev && !apt_bar_dev) {   // zero cotangent: exact zeros, no pass
+            check_hip(hipMemsetAsync(grad_dev, 0, sizeof(double) * np * (size_t)nconf, h.stream), "memset grad");
+            return;
+        }
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events (as cf_compute_batch); no workspace: the pass of cf_compute_batch_lj_vjp
+        const int pass = batch_lj_pass_size(H, nconf);
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            cf::launch_batch_dipole_vjp(h, m, pos_dev + 3 * n * c0, dipole_bar_dev ? dipole_bar_dev + 3 * (size_t)c0 : nullptr,
+                                        apt_bar_dev ? apt_bar_dev + 9 * n * c0 : nullptr, grad_dev + np * c0);
+            H->batch_passes++;
+        }
+        launch_check(h, "compute_batch_dipole_vjp");
+    });
+}
+
+// synchronous host form: positions and cotangents up through the same staging buffer, the gradients back
+CF_EXPORT int cf_compute_batch_dipole_vjp_host(cf_handle* H, int32_t nconf, const double* pos_host,
+                                               const double* dipole_bar_host, const double* apt_bar_host,
+                                               double* grad_host) {
+    return guarded([&] {
+        batch_vjp_precheck(H, nconf, pos_host, grad_host, "cf_compute_batch_dipole_vjp_host");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, B = (size_t)nconf;
+        const size_t np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+        double* pos = batch_dipole_stage(H, nconf, np);
+        double* mb = pos + 3 * n * B;
+        double* pb = mb + 3 * B;
+        double* grad = pb + 9 * n * B;
+        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D positions");
+        if (dipole_bar_host)
+            check_hip(hipMemcpyAsync(mb, dipole_bar_host, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h.stream),
+                      "H2D dipole cotangent");
+        if (apt_bar_host)
+            check_hip(hipMemcpyAsync(pb, apt_bar_host, sizeof(double) * 9 * n * B, hipMemcpyHostToDevice, h.stream),
+                      "H2D polar tensor cotangent");
+        const int rc = cf_compute_batch_dipole_vjp(H, nconf, pos, dipole_bar_host ? mb : nullptr,
+                                                   apt_bar_host ? pb : nullptr, grad);
+        if (rc != CF_OK) throw CfError(rc, g_err);
+        check_hip(hipMemcpyAsync(grad_host, grad, sizeof(double) * np * B, hipMemcpyDeviceToHost, h.stream), "D2H grad");
         check_hip(hipStreamSynchronize(h.stream), "sync");
     });
 }

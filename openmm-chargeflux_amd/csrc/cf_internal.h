@@ -413,6 +413,18 @@ void launch_batch_pbc_vjp(Handle& h, const BatchPbcWs& w, const BatchPbcGradWs& 
 void launch_batch_lj_vjp(Handle& h, int nconf, const double* pos, const double* boxes, const double* e_bar,
                          const double* f_bar, double* grad);
 
+// dipoles and atomic polar tensors of the non-periodic batch (cf_kernels_batch_dipole.hip,
+// cf_compute_batch_dipole): one pass of nconf <= w.cap conformations on h.stream, at most three
+// launches (k_b_flux and k_b_charges into w, then k_bd_apt).  dipole [nconf][3], apt [nconf][N][3][3],
+// charges [nconf][N]: device, overwritten, each may be null
+void launch_batch_dipole(Handle& h, const BatchWs& w, int nconf, const double* pos, double* dipole, double* apt,
+                         double* charges);
+// their parameter gradients (cf_compute_batch_dipole_vjp): one pass of nconf <= kBatchMaxPass
+// conformations on h.stream, at most two launches, no workspace.  dipole_bar [nconf][3], apt_bar
+// [nconf][N][3][3]: device or null (= zero); grad [nconf][N + 2 nb + 2 na + 5 nw] overwritten
+void launch_batch_dipole_vjp(Handle& h, int nconf, const double* pos, const double* dipole_bar, const double* apt_bar,
+                             double* grad);
+
 void check_hip(hipError_t e, const char* what);
 
 // ---- fp64 math helpers shared by the pair and grid kernels -------------------------

@@ -153,6 +153,10 @@ SIGNATURES = [
     ("cf_compute_batch_periodic_vjp_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP, DP, DP, DP]),
     ("cf_compute_batch_lj_vjp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, DP, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cf_compute_batch_lj_vjp_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP, DP, DP]),
+    ("cf_compute_batch_dipole", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cf_compute_batch_dipole_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP, DP]),
+    ("cf_compute_batch_dipole_vjp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cf_compute_batch_dipole_vjp_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP, DP]),
 ]
 
 _lib = None

@@ -19,6 +19,14 @@ inputs does.  Without them the LJ parameters are taken from `force` unchanged an
 one above: no extra call.  All run in libchargeflux_hip.so.  Gradients exist for the parameters
 only -- not for the positions or the boxes.
 
+    dipoles, apts = model.dipoles(q, bonds, angles, waters, positions)   # non-periodic: (B,3), (B,N,3,3)
+    loss = ((dipoles - target) ** 2).sum()
+    loss.backward()                                   # q.grad, bonds.grad, angles.grad, waters.grad
+
+dipoles() is cf_compute_batch_dipole forward and one cf_compute_batch_dipole_vjp backward: the dipole
+mu = sum_a q_a x_a about the coordinate origin (that of a charged system moves with a translation) and
+the atomic polar tensors apts[c, b, i, j] = d mu_i / d x_bj, charge-flux part included.
+
 Convention (cf_compute_batch_lj_vjp): an atom with epsilon = 0 receives exactly 0 for its sigma and
 epsilon gradients.  The true derivative of sqrt(eps_i eps_j) is singular there; such an atom has no
 LJ interaction, and an optimiser leaves it at 0.
@@ -84,6 +92,46 @@ class _BatchFn(torch.autograd.Function):
             for slot, (t, need) in enumerate(zip(ctx.lj, ctx.needs_input_grad[5:7])):
                 lj[slot] = g[slot * n:(slot + 1) * n].reshape(t.shape).to(t.device) if need else None
         return (None, *out, *lj, None, None)
+
+
+class _DipoleFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, charges, bonds, angles, waters, positions):
+        params = tuple(t.detach().to("cpu", torch.float64).contiguous() for t in (charges, bonds, angles, waters))
+        model._load(params)
+        k = model.kernel
+        nconf, n = positions.shape[0], positions.shape[1]
+        dipoles = torch.empty((nconf, 3), dtype=torch.float64, device=positions.device)
+        apts = torch.empty((nconf, n, 3, 3), dtype=torch.float64, device=positions.device)
+        model._before()
+        k.execute_batch_dipole_device(positions, dipoles, apts)
+        model._after()
+        ctx.set_materialize_grads(False)   # an output the loss does not use: a None (NULL) cotangent
+        ctx.model, ctx.params, ctx.loaded = model, params, model._loads
+        ctx.inputs = (charges, bonds, angles, waters)
+        ctx.save_for_backward(positions)
+        return dipoles, apts
+
+    @staticmethod
+    def backward(ctx, dipole_bar, apt_bar):
+        model = ctx.model
+        k = model.kernel
+        (positions,) = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[1:5]):
+            return (None,) * 6
+        if model._loads != ctx.loaded:   # another forward has changed the parameters since: put these back
+            model._load(ctx.params)
+            ctx.loaded = model._loads
+        cot = [None if t is None else t.detach().to(torch.float64).contiguous() for t in (dipole_bar, apt_bar)]
+        counts = k.param_counts()
+        grad = torch.empty((positions.shape[0], sum(counts)), dtype=torch.float64, device=positions.device)
+        model._before()
+        k.execute_batch_dipole_vjp_device(positions, grad, *cot)
+        model._after()
+        g = k.split_gradient(grad.sum(dim=0, keepdim=True), counts)
+        out = [g[name][0].reshape(t.shape).to(t.device) if need else None
+               for t, name, need in zip(ctx.inputs, ("charges", "bonds", "angles", "waters"), ctx.needs_input_grad[1:5])]
+        return (None, *out, None)
 
 
 class BatchedChargeFlux:
@@ -163,3 +211,18 @@ class BatchedChargeFlux:
         if boxes is not None:   # before the parameters are loaded
             self.kernel._batch_boxes(boxes, positions.shape[0])
         return _BatchFn.apply(self, charges, bonds, angles, waters, sigmas, epsilons, positions, boxes)
+
+    def dipoles(self, charges, bonds, angles, waters, positions):
+        """Dipoles (B,3) and atomic polar tensors (B,N,3,3) of B conformations of a non-periodic
+        system as a differentiable function of the four parameter tensors (arguments as __call__;
+        cf_compute_batch_dipole forward, one cf_compute_batch_dipole_vjp summed over the
+        conformations in backward; an output the loss does not use gives a NULL cotangent).  The
+        dipole is taken about the coordinate origin: for a charged system it moves with a
+        translation.  apts[c, b, i, j] = d dipole_i / d x_bj."""
+        for t, name in ((charges, "charges"), (bonds, "bonds"), (angles, "angles"), (waters, "waters"),
+                        (positions, "positions")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise ValueError(f"{name} must be a float64 torch tensor")
+        if positions.requires_grad:
+            raise ValueError("positions must not require grad: gradients with respect to positions are not computed")
+        return _DipoleFn.apply(self, charges, bonds, angles, waters, positions)

@@ -468,6 +468,75 @@ class HipCalcCoulForceKernel:
         _cabi.check(self._lib.cf_compute_batch_lj_vjp(self._h, nconf, ptr(positions), _dp(b) if b is not None else None,
                                                       ptr(energy_bar), ptr(forces_bar), ptr(grad)), self._lib)
 
+    # dipoles and atomic polar tensors of the non-periodic batch (cf_compute_batch_dipole, _vjp) --------
+    def execute_batch_dipole_host(self, positions):
+        """Dipoles and atomic polar tensors of B conformations (cf_compute_batch_dipole_host;
+        non-periodic systems).  positions (B,N,3): C-contiguous float64 numpy array.  Returns
+        (dipoles (B,3) in e nm about the coordinate origin, apts (B,N,3,3) with apts[c, b, i, j] =
+        d dipole_i / d x_bj in e, charges (B,N) after flux: execute_batch_host's, to the bit)."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        dipoles, apts, charges = np.zeros((nconf, 3)), np.zeros((nconf, self._n, 3, 3)), np.zeros((nconf, self._n))
+        _cabi.check(self._lib.cf_compute_batch_dipole_host(self._h, nconf, _dp(positions), _dp(dipoles), _dp(apts),
+                                                           _dp(charges)), self._lib)
+        return dipoles, apts, charges
+
+    def execute_batch_dipole_device(self, positions, dipoles=None, apts=None, charges=None):
+        """The same on torch tensors (float64, on the kernel's device, contiguous): positions
+        (B,N,3); dipoles (B,3), apts (B,N,3,3) and charges (B,N) overwritten, each may be None.
+        Asynchronous on the kernel's stream."""
+        import torch
+        if not isinstance(positions, torch.Tensor):
+            raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
+        for t, name, trailing in ((dipoles, "dipoles", (3,)), (apts, "apts", (self._n, 3, 3)),
+                                  (charges, "charges", (self._n,))):
+            if t is not None and (not isinstance(t, torch.Tensor)
+                                  or self._check_batch_array(t, name, trailing, torch) != nconf):
+                raise ValueError(f"{name} must be a float64 torch tensor for {nconf} conformations")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _cabi.check(self._lib.cf_compute_batch_dipole(self._h, nconf, ptr(positions), ptr(dipoles), ptr(apts),
+                                                      ptr(charges)), self._lib)
+
+    def _check_dipole_cotangents(self, nconf, dipole_bar, apt_bar, module, kind):
+        for t, name, trailing in ((dipole_bar, "dipole_bar", (3,)), (apt_bar, "apt_bar", (self._n, 3, 3))):
+            if t is not None and (not isinstance(t, kind)
+                                  or self._check_batch_array(t, name, trailing, module) != nconf):
+                raise ValueError(f"{name} must be a float64 {kind.__name__} for {nconf} conformations")
+
+    def execute_batch_dipole_vjp_host(self, positions, dipole_bar=None, apt_bar=None):
+        """Gradients of L = dipole_bar . dipole + apt_bar : apt with respect to the base charges and
+        the flux parameters, per conformation (cf_compute_batch_dipole_vjp_host).  positions (B,N,3),
+        dipole_bar (B,3), apt_bar (B,N,3,3): C-contiguous float64 numpy arrays, a cotangent may be
+        None (= zero).  Returns the dict of execute_batch_vjp_host (split_gradient)."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        self._check_dipole_cotangents(nconf, dipole_bar, apt_bar, np, np.ndarray)
+        counts = self.param_counts()
+        flat = np.zeros((nconf, sum(counts)))
+        opt = lambda a: _dp(a) if a is not None else None
+        _cabi.check(self._lib.cf_compute_batch_dipole_vjp_host(self._h, nconf, _dp(positions), opt(dipole_bar),
+                                                               opt(apt_bar), _dp(flat)), self._lib)
+        return self.split_gradient(flat, counts)
+
+    def execute_batch_dipole_vjp_device(self, positions, grad, dipole_bar=None, apt_bar=None):
+        """The same on torch tensors (float64, on the kernel's device, contiguous): grad (B,P) is
+        overwritten (split_gradient gives its views).  Asynchronous on the kernel's stream."""
+        import torch
+        if not isinstance(positions, torch.Tensor):
+            raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
+        self._check_dipole_cotangents(nconf, dipole_bar, apt_bar, torch, torch.Tensor)
+        if not isinstance(grad, torch.Tensor):
+            raise ValueError("grad must be a torch tensor of shape (B, P)")
+        if self._check_batch_array(grad, "grad", (sum(self.param_counts()),), torch) != nconf:
+            raise ValueError(f"grad must hold {nconf} conformations")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _cabi.check(self._lib.cf_compute_batch_dipole_vjp(self._h, nconf, ptr(positions), ptr(dipole_bar),
+                                                          ptr(apt_bar), ptr(grad)), self._lib)
+
     def set_batch_limit(self, n: int):
         """Conformations evaluated per pass of a batch (bounds the batch workspace); 0 = automatic
         (a 256 MiB workspace).  Results do not depend on it."""
