@@ -36,7 +36,8 @@ extern "C" {
                               cf_compute_batch_periodic_vjp_host; cf_compute_batch_lj_vjp,
                               cf_compute_batch_lj_vjp_host; cf_compute_batch_dipole,
                               cf_compute_batch_dipole_host, cf_compute_batch_dipole_vjp,
-                              cf_compute_batch_dipole_vjp_host */
+                              cf_compute_batch_dipole_vjp_host; cf_compute_batch_hvp,
+                              cf_compute_batch_hvp_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -573,12 +574,59 @@ CF_EXPORT int cf_compute_batch_dipole_vjp(cf_handle* h, int32_t nconf, const dou
 CF_EXPORT int cf_compute_batch_dipole_vjp_host(cf_handle* h, int32_t nconf, const double* pos_host,
                                                const double* dipole_bar_host, const double* apt_bar_host,
                                                double* grad_host);
+/*
+ * Hessian-vector products of the non-periodic batch -- normal modes (with the polar tensors: IR
+ * spectra), Newton-CG geometry optimisation, harmonic validation of a fitted model.  H = d2E/dxdx is
+ * the Hessian with respect to the positions of exactly the energy cf_compute_batch returns with both
+ * flags: all non-excluded pairs, Coulomb with the charges after flux, LJ, the handle's one_4pi_eps0.
+ * Per conformation c and direction k:   out[c][k] = H(x_c) v_ck = -D_v F,   F = cf_compute_batch's
+ * forces, D_v the directional derivative along v.
+ *   pos_dev   [nconf][N][3] fp64 DEVICE, conformation-major (nm)
+ *   vec_dev   [nconf][nvec][N][3] fp64 DEVICE (nm): nvec directions per conformation
+ *   out_dev   [nconf][nvec][N][3] fp64 DEVICE, OVERWRITTEN (kJ/mol/nm^2 times the unit of v)
+ * The nvec directions of a conformation share its positions: flux, charges and dq/dx are computed once
+ * per conformation.  The 3N unit vectors give the full Hessian, one row (= column) per direction.
+ * Closed form, no finite differences anywhere: with d = x_j - x_i, w = v_j - v_i, qdot = D_v q and
+ * D = dq/dx,
+ *   (H v)_i = sum_j (sdot d + s w) + sum_a (gdot_a D_ai + g_a Ddot_ai)
+ *   s    = (A + C) / r^2,  A = e4 s6 (12 s6 - 6),  C = ke q_i q_j / r      (the forward pair term)
+ *   sdot = [e4 s6 (48 - 168 s6) - 3 C] (d.w) / r^4 + ke (qdot_i q_j + q_i qdot_j) / r^3
+ *   g_a  = ke sum_j q_j / r,  gdot_a = ke sum_j [qdot_j / r - q_j (d.w) / r^3]
+ * over the non-excluded j != i, and Ddot = D_v D from the flux terms' own expressions evaluated on
+ * (value, tangent) pairs.  Nothing divides by a parameter: a term with k = 0 is legal.
+ * A pass is at most six kernel launches whatever nconf and nvec (flux terms, charges, term tangents,
+ * charge tangents, all pairs, chain rule), in the workspace of cf_compute_batch plus, per
+ * (conformation, direction), the slot tangents, the tangent of dq/dx, qdot[N], g[N] and gdot[N].  No
+ * atomics; every sum's order depends only on N and the topology, so the row of a (conformation,
+ * direction) is bitwise the same alone, at any position of any batch, for any nvec, under any pass
+ * size and in the host and the device form.
+ *
+ * Errors and states as cf_compute_batch_vjp: a periodic handle CF_ERR_INVALID; world_size > 1 or a
+ * call between cf_compute_begin and _end CF_ERR_STATE; NULL pos, vec or out, nconf < 0 or nvec < 0
+ * CF_ERR_INVALID; nconf = 0 or nvec = 0 is a no-op that counts nothing; a NULL handle is rejected
+ * without touching a device; a guard bit already set fails the call.  Always fp64, eager launches on
+ * the handle's stream (never captured or replayed, not recorded by cf_set_timing), asynchronous:
+ * inputs and outputs must stay valid until the stream reaches them.  cf_get_batch_stats counts the
+ * call, its nconf conformations and its passes; cf_compute's state and diagnostics are not touched; it
+ * reads the parameter buffers cf_update_parameters last wrote.  No guard bits.  Out of scope: periodic
+ * handles, the derivative of H with respect to the parameters.
+ */
+CF_EXPORT int cf_compute_batch_hvp(cf_handle* h, int32_t nconf, const double* pos_dev, int32_t nvec,
+                                   const double* vec_dev, double* out_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_hvp_host(cf_handle* h, int32_t nconf, const double* pos_host, int32_t nvec,
+                                        const double* vec_host, double* out_host);
 /* cap on the conformations evaluated per pass (bounds the batch workspace); 0 = automatic: as many
  * as keep the workspace (per conformation q[N], the flux slots, dq/dx, dE/dq[N], F[3N], e[N]; a
  * periodic batch also the phase tables, 4 doubles per [N][kmax_x + kmax_y + kmax_z] entry, and 3
  * doubles per k-vector; cf_compute_batch_vjp also qdot[N], g[N], a[N]; cf_compute_batch_periodic_vjp
  * those three and 2 more doubles per k-vector) at or below 256 MiB, and never more than 65535
- * (cf_compute_batch_lj_vjp and cf_compute_batch_dipole_vjp have no workspace: automatic is 65535).  A
+ * (cf_compute_batch_lj_vjp and cf_compute_batch_dipole_vjp have no workspace: automatic is 65535).
+ * cf_compute_batch_hvp: a pass is conformations x directions with conformations * directions <= 65535;
+ * per conformation the doubles of cf_compute_batch, per (conformation, direction) S + 3 D + 3 N more
+ * (S charge slots: 2 per bond, 3 per angle or water; D dq/dx entries: 4 per bond, 9 per angle or
+ * water); the limit caps its conformations, and a conformation whose nvec directions alone exceed
+ * 256 MiB or 65535 takes its directions in several passes.  A
  * larger batch runs as consecutive passes.  Applies to every batch form; cf_get_batch_stats counts
  * them all (a VJP call with all cotangents NULL counts its call and conformations, and no pass). */
 CF_EXPORT int cf_set_batch_limit(cf_handle* h, int32_t max_conformations);

@@ -90,6 +90,11 @@ struct cf_handle {
     // batch_dipole_stage (in H->allocs)
     double* batch_dipole_stage = nullptr;
     int64_t batch_dipole_stage_confs = 0;
+    // cf_compute_batch_hvp: the extra workspace beside `batch`, a row per (conformation, direction)
+    // of a pass, and the host form's staging buffer: pos, directions, products (both in H->allocs)
+    cf::BatchHvpWs batch_hvp;
+    double* batch_hvp_stage = nullptr;
+    size_t batch_hvp_stage_doubles = 0;
 };
 
 namespace {
@@ -2451,6 +2456,108 @@ CF_EXPORT int cf_compute_batch_dipole_vjp_host(cf_handle* H, int32_t nconf, cons
                                                    apt_bar_host ? pb : nullptr, grad);
         if (rc != CF_OK) throw CfError(rc, g_err);
         check_hip(hipMemcpyAsync(grad_host, grad, sizeof(double) * np * B, hipMemcpyDeviceToHost, h.stream), "D2H grad");
+        check_hip(hipStreamSynchronize(h.stream), "sync");
+    });
+}
+
+// ---- Hessian-vector products of the non-periodic batch (cf_kernels_batch_hvp.hip) -------------------
+// Everything that can refuse the call, before anything is launched, staged or counted.
+static void batch_hvp_precheck(cf_handle* H, int32_t nconf, const double* pos, int32_t nvec, const double* vec,
+                               const double* out, const char* name) {
+    if (!H || !pos || !vec || !out) fail(CF_ERR_INVALID, "null argument");
+    if (nconf < 0) fail(CF_ERR_INVALID, "nconf must be >= 0");
+    if (nvec < 0) fail(CF_ERR_INVALID, "nvec must be >= 0");
+    cf::Handle& h = H->h;
+    if (h.world > 1) fail(CF_ERR_STATE, std::string(name) + " is single-rank only");
+    if (h.pbc) fail(CF_ERR_INVALID, std::string(name) + ": batches are non-periodic only (this handle is periodic)");
+    if (h.pending_flags >= 0) fail(CF_ERR_STATE, std::string(name) + " during a begun evaluation");
+    guard_check(h);
+}
+
+// A pass is m conformations x kv of their directions: m * kv <= 65535 rows (gridDim.y).  Automatic:
+// kv = as many of the nvec directions as one conformation's workspace holds within kBatchAutoBytes
+// (all of them, but for a very large N or nvec), then as many conformations as fit; cf_set_batch_limit
+// replaces the automatic conformation count.
+static void batch_hvp_pass_size(const cf_handle* H, int nconf, int nvec, int& m, int& kv) {
+    const size_t per_c = cf::batch_doubles_per_conf(H->h) * sizeof(double);
+    const size_t per_v = cf::batch_hvp_doubles_per_row(H->h) * sizeof(double);
+    const size_t room = kBatchAutoBytes > per_c ? (kBatchAutoBytes - per_c) / per_v : 0;
+    kv = (int)std::min<size_t>(std::min<size_t>((size_t)nvec, (size_t)cf::kBatchMaxPass), std::max<size_t>(1, room));
+    int64_t lim = H->batch_limit > 0 ? H->batch_limit
+                                     : (int64_t)std::max<size_t>(1, kBatchAutoBytes / (per_c + (size_t)kv * per_v));
+    lim = std::min<int64_t>(lim, cf::kBatchMaxPass / kv);
+    m = (int)std::min<int64_t>(lim, nconf);
+}
+
+CF_EXPORT int cf_compute_batch_hvp(cf_handle* H, int32_t nconf, const double* pos_dev, int32_t nvec,
+                                   const double* vec_dev, double* out_dev) {
+    return guarded([&] {
+        batch_hvp_precheck(H, nconf, pos_dev, nvec, vec_dev, out_dev, "cf_compute_batch_hvp");
+        if (nconf == 0 || nvec == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        int pass = 0, kv = 0;
+        batch_hvp_pass_size(H, nconf, nvec, pass, kv);
+        if (pass > H->batch.cap) {   // first call or growth: allocates (and so synchronises)
+            double* old = H->batch.base;
+            H->batch = cf::BatchWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_carve(h, base, pass, H->batch);
+        }
+        if (pass * kv > H->batch_hvp.cap) {
+            double* old = H->batch_hvp.base;
+            H->batch_hvp = cf::BatchHvpWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_hvp_doubles_per_row(h) * (size_t)pass * (size_t)kv);
+            cf::batch_hvp_carve(h, base, pass * kv, H->batch_hvp);
+        }
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events (as cf_compute_batch)
+        const size_t n = (size_t)h.n, vstride = 3 * n * (size_t)nvec;
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            for (int k0 = 0; k0 < nvec; k0 += kv) {
+                const size_t at = vstride * (size_t)c0 + 3 * n * (size_t)k0;
+                cf::launch_batch_hvp(h, H->batch, H->batch_hvp, m, std::min(kv, nvec - k0), pos_dev + 3 * n * c0,
+                                     vec_dev + at, (long)vstride, out_dev + at);
+                H->batch_passes++;
+            }
+        }
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        launch_check(h, "compute_batch_hvp");
+    });
+}
+
+// synchronous host form: positions and directions up through the handle's staging buffer, the products back
+CF_EXPORT int cf_compute_batch_hvp_host(cf_handle* H, int32_t nconf, const double* pos_host, int32_t nvec,
+                                        const double* vec_host, double* out_host) {
+    return guarded([&] {
+        batch_hvp_precheck(H, nconf, pos_host, nvec, vec_host, out_host, "cf_compute_batch_hvp_host");
+        if (nconf == 0 || nvec == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, B = (size_t)nconf, K = (size_t)nvec;
+        const size_t need = 3 * n * B * (1 + 2 * K);
+        if (need > H->batch_hvp_stage_doubles) {
+            double* old = H->batch_hvp_stage;
+            H->batch_hvp_stage = nullptr; H->batch_hvp_stage_doubles = 0;
+            dfree(H, old);
+            H->batch_hvp_stage = dalloc<double>(H, need);
+            H->batch_hvp_stage_doubles = need;
+        }
+        double* pos = H->batch_hvp_stage;
+        double* vec = pos + 3 * n * B;
+        double* out = vec + 3 * n * B * K;
+        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D positions");
+        check_hip(hipMemcpyAsync(vec, vec_host, sizeof(double) * 3 * n * B * K, hipMemcpyHostToDevice, h.stream),
+                  "H2D directions");
+        const int rc = cf_compute_batch_hvp(H, nconf, pos, nvec, vec, out);
+        if (rc != CF_OK) throw CfError(rc, g_err);
+        check_hip(hipMemcpyAsync(out_host, out, sizeof(double) * 3 * n * B * K, hipMemcpyDeviceToHost, h.stream),
+                  "D2H products");
         check_hip(hipStreamSynchronize(h.stream), "sync");
     });
 }

@@ -425,6 +425,26 @@ void launch_batch_dipole(Handle& h, const BatchWs& w, int nconf, const double* p
 void launch_batch_dipole_vjp(Handle& h, int nconf, const double* pos, const double* dipole_bar, const double* apt_bar,
                              double* grad);
 
+// Hessian-vector products of the non-periodic batch (cf_kernels_batch_hvp.hip, cf_compute_batch_hvp):
+// the extra workspace of one pass beside BatchWs, one row per (conformation, direction) of the pass,
+// carved from one allocation of cap * batch_hvp_doubles_per_row doubles
+struct BatchHvpWs {
+    double* base = nullptr;
+    int cap = 0;                // rows the arrays hold
+    double* dslot = nullptr;    // [cap][S] tangents of the charge slots along the direction
+    double* ddot = nullptr;     // [cap][D*3] tangent of dq/dx
+    double* qdot = nullptr;     // [cap][N] tangent of the charges
+    double* g = nullptr;        // [cap][N] dE/dq
+    double* gdot = nullptr;     // [cap][N] its tangent
+};
+size_t batch_hvp_doubles_per_row(const Handle& h);
+void batch_hvp_carve(const Handle& h, double* base, int cap, BatchHvpWs& w);
+// one pass of nconf <= w.cap conformations x kv directions (nconf * kv <= min(hw.cap, kBatchMaxPass)
+// rows) on h.stream: at most six launches.  pos [nconf][N][3]; vec and out: direction k of
+// conformation c at c * vstride + k * 3 N doubles; out overwritten
+void launch_batch_hvp(Handle& h, const BatchWs& w, const BatchHvpWs& hw, int nconf, int kv, const double* pos,
+                      const double* vec, long vstride, double* out);
+
 void check_hip(hipError_t e, const char* what);
 
 // ---- fp64 math helpers shared by the pair and grid kernels -------------------------

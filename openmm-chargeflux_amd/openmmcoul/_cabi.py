@@ -157,6 +157,8 @@ SIGNATURES = [
     ("cf_compute_batch_dipole_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP, DP]),
     ("cf_compute_batch_dipole_vjp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cf_compute_batch_dipole_vjp_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP, DP]),
+    ("cf_compute_batch_hvp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("cf_compute_batch_hvp_host", C.c_int, [C.c_void_p, C.c_int32, DP, C.c_int32, DP, DP]),
 ]
 
 _lib = None

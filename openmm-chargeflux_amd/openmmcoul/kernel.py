@@ -537,6 +537,61 @@ class HipCalcCoulForceKernel:
         _cabi.check(self._lib.cf_compute_batch_dipole_vjp(self._h, nconf, ptr(positions), ptr(dipole_bar),
                                                           ptr(apt_bar), ptr(grad)), self._lib)
 
+    # Hessian-vector products of the non-periodic batch (cf_compute_batch_hvp) --------------------------
+    def _check_hvp_vectors(self, vectors, nconf, module, kind):
+        if not isinstance(vectors, kind):
+            raise ValueError(f"vectors must be a float64 {kind.__name__} of shape (B, K, N, 3)")
+        shape = tuple(vectors.shape)
+        if len(shape) != 4:
+            raise ValueError(f"vectors must have shape (B, K, N, 3), got {shape}")
+        if self._check_batch_array(vectors, "vectors", (shape[1], self._n, 3), module) != nconf:
+            raise ValueError(f"vectors holds {shape[0]} conformations, positions {nconf}")
+        return shape[1]
+
+    def execute_batch_hvp_host(self, positions, vectors):
+        """Hessian-vector products of B conformations (cf_compute_batch_hvp_host; non-periodic
+        systems).  positions (B,N,3) in nm, vectors (B,K,N,3): C-contiguous float64 numpy arrays, K
+        directions per conformation.  Returns (B,K,N,3): H(x_b) v_bk, with H = d2E/dxdx of the energy
+        execute_batch_host returns (kJ/mol/nm^2 for v in nm)."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        nvec = self._check_hvp_vectors(vectors, nconf, np, np.ndarray)
+        out = np.zeros((nconf, nvec, self._n, 3))
+        _cabi.check(self._lib.cf_compute_batch_hvp_host(self._h, nconf, _dp(positions), nvec, _dp(vectors), _dp(out)),
+                    self._lib)
+        return out
+
+    def execute_batch_hvp_device(self, positions, vectors, out=None):
+        """The same on torch tensors (float64, on the kernel's device, contiguous): out (B,K,N,3) is
+        overwritten (created if None) and returned.  Asynchronous on the kernel's stream."""
+        import torch
+        if not isinstance(positions, torch.Tensor):
+            raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
+        nvec = self._check_hvp_vectors(vectors, nconf, torch, torch.Tensor)
+        if out is None:
+            out = torch.empty_like(vectors)
+        elif (not isinstance(out, torch.Tensor)
+              or self._check_batch_array(out, "out", (nvec, self._n, 3), torch) != nconf):
+            raise ValueError("out must be a float64 torch tensor shaped like vectors")
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        _cabi.check(self._lib.cf_compute_batch_hvp(self._h, nconf, ptr(positions), nvec, ptr(vectors), ptr(out)),
+                    self._lib)
+        return out
+
+    def hessians_host(self, positions, symmetrize=True):
+        """Full Hessians (B,3N,3N) of B conformations: one execute_batch_hvp_host call with the 3N unit
+        vectors per conformation, symmetrised as (H + H^T) / 2 (symmetrize=False: the products as they
+        come, row k = H e_k)."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        n3 = 3 * self._n
+        units = np.ascontiguousarray(np.broadcast_to(np.eye(n3).reshape(n3, self._n, 3), (nconf, n3, self._n, 3)))
+        hess = self.execute_batch_hvp_host(positions, units).reshape(nconf, n3, n3)
+        return 0.5 * (hess + hess.transpose(0, 2, 1)) if symmetrize else hess
+
     def set_batch_limit(self, n: int):
         """Conformations evaluated per pass of a batch (bounds the batch workspace); 0 = automatic
         (a 256 MiB workspace).  Results do not depend on it."""
