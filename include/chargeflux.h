@@ -37,7 +37,8 @@ extern "C" {
                               cf_compute_batch_lj_vjp_host; cf_compute_batch_dipole,
                               cf_compute_batch_dipole_host, cf_compute_batch_dipole_vjp,
                               cf_compute_batch_dipole_vjp_host; cf_compute_batch_hvp,
-                              cf_compute_batch_hvp_host */
+                              cf_compute_batch_hvp_host; cf_compute_batch_periodic_hvp,
+                              cf_compute_batch_periodic_hvp_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -609,13 +610,74 @@ CF_EXPORT int cf_compute_batch_dipole_vjp_host(cf_handle* h, int32_t nconf, cons
  * inputs and outputs must stay valid until the stream reaches them.  cf_get_batch_stats counts the
  * call, its nconf conformations and its passes; cf_compute's state and diagnostics are not touched; it
  * reads the parameter buffers cf_update_parameters last wrote.  No guard bits.  Out of scope: periodic
- * handles, the derivative of H with respect to the parameters.
+ * handles (cf_compute_batch_periodic_hvp below), the derivative of H with respect to the parameters.
  */
 CF_EXPORT int cf_compute_batch_hvp(cf_handle* h, int32_t nconf, const double* pos_dev, int32_t nvec,
                                    const double* vec_dev, double* out_dev);
 /* synchronous host-memory form of the same (H2D, evaluate, D2H) */
 CF_EXPORT int cf_compute_batch_hvp_host(cf_handle* h, int32_t nconf, const double* pos_host, int32_t nvec,
                                         const double* vec_host, double* out_host);
+/*
+ * Hessian-vector products of the periodic batch -- normal modes and phonons of ice and small liquid
+ * boxes, Newton-CG relaxation of condensed-phase frames, the harmonic check of a fitted model on its
+ * own NVT / NPT frames.  Per conformation c, its box and direction k:
+ *   out[c][k] = H(x_c; box_c) v_ck = -D_v F,   F = the forces cf_compute_batch_periodic returns for that
+ * conformation and box with both flags: fp64, the exact k-sum over the half-space k set with k from
+ * the box diagonals, all pairs by minimum image within the cutoff, LJ, the erf correction of every
+ * excluded pair at any distance, the chain rule through the flux charges, cf_create's alpha and kmax,
+ * the handle's one_4pi_eps0.  The box is fixed, as are the pair set and the image of every pair: the
+ * derivative is the one of the forces as evaluated.  A pair exactly at the cutoff or at a
+ * minimum-image face contributes by the rule the forward kernel applies to it (r2 <= rc2, delta_r),
+ * with no surface term.
+ *   pos_dev, vec_dev, out_dev   as cf_compute_batch_hvp ([nconf][N][3], [nconf][nvec][N][3] DEVICE; out
+ *                               OVERWRITTEN)
+ *   boxes_host                  as cf_compute_batch_periodic: [nconf][9] fp64 HOST, copied to a pinned
+ *                               buffer before the call returns; every box checked by cf_compute's rules
+ *                               before anything is launched or counted (CF_ERR_INVALID names the
+ *                               conformation)
+ * Closed form.  With d the minimum image of x_i - x_j, r = |d|, w = v_i - v_j, qdot = D_v q, D = dq/dx,
+ * Ddot = D_v D, c = 2 / sqrt(pi), c_s = ke alpha / sqrt(pi):
+ *   (H v)_i = -D_v F_i^pair - D_v F_i^recip + sum_a (gdot_a D_ai + g_a Ddot_ai)
+ * Pair part, over the non-excluded j within the cutoff (phi r = P = erfc(alpha r)) and the excluded j at
+ * any distance (P = -erf(alpha r), no LJ), with Q = -phi' r^2 = P + c alpha r e^{-alpha^2 r^2}:
+ *   F_i^pair = sum_j s d,   s = (A + C Q) / r^2,  A = e4 s6 (12 s6 - 6),  C = ke q_i q_j / r
+ *   D_v F_i^pair = sum_j (sdot d + s w)
+ *   sdot = [e4 s6 (48 - 168 s6) - C (3 Q + 2 c (alpha r)^3 e^{-alpha^2 r^2})] (d.w) / r^4
+ *          + ke Q (qdot_i q_j + q_i qdot_j) / r^3
+ * (phi'' in closed form from the erfc(alpha r) and e^{-alpha^2 r^2} the forward table lookup returns; the
+ * table is not differentiated).  Reciprocal part, with A_k = 2 c_k S(k), B_k = 2 c_k Sdot(k),
+ * Sdot = sum_j (qdot_j + i q_j kappa_j) e_j, e_i = e^{i k.x_i}, kappa_i = k.v_i, and the forward kernel's
+ * F_i^recip = q_i sum_k k G_ik,  G_ik = Re A_k Im e_i - Im A_k Re e_i:
+ *   D_v F_i^recip = qdot_i sum_k k G_ik + q_i sum_k k (Re B_k Im e_i - Im B_k Re e_i + kappa_i Re[conj(e_i) A_k])
+ *   g_i    = ke sum_j q_j P / r - 2 c_s q_i + sum_k Re[conj(e_i) A_k]
+ *   gdot_i = ke sum_j (P qdot_j - Q q_j (d.w) / r^2) / r - 2 c_s qdot_i + sum_k (Re[conj(e_i) B_k] - kappa_i G_ik)
+ * Ddot and qdot come from the flux terms' own expressions on (value, tangent) pairs, every difference
+ * vector the minimum image and its tangent the plain difference of the atoms' tangents (the image
+ * shift is piecewise constant).  Nothing divides by a parameter: a term with k = 0 is legal.
+ * The work per pair and per (atom, k) that does not depend on the direction is done once for a chunk
+ * of 4 directions of a conformation.  A pass is at most nine launches (flux terms, charges, phase
+ * tables, term tangents, charge tangents, structure factors, pairs, reciprocal part, chain rule).  No
+ * atomics; every sum's order depends only on N, the topology and kmax, so the row of a (conformation,
+ * direction) is bitwise the same alone, at any position of any batch, for any nvec, in any slot of a
+ * chunk, under any pass size and in the host and the device form.
+ *
+ * Errors and states as cf_compute_batch_periodic_vjp: a non-periodic handle CF_ERR_INVALID;
+ * world_size > 1 or a call between cf_compute_begin and _end CF_ERR_STATE; NULL pos, boxes, vec or
+ * out, nconf < 0 or nvec < 0 CF_ERR_INVALID; nconf = 0 or nvec = 0 is a no-op that counts nothing; a
+ * NULL handle is rejected without touching a device; a guard bit already set fails the call.  Always
+ * fp64, eager launches on the handle's stream (never captured or replayed, not recorded by
+ * cf_set_timing), asynchronous.  cf_get_batch_stats counts the call, its nconf conformations and its
+ * passes; cf_compute's state and diagnostics are not touched, and the forward periodic batch and both
+ * periodic VJPs return the same bits before and after.  No guard bits.  Out of scope: the derivative
+ * with respect to the box (stress, elastic constants) and of H with respect to the parameters.
+ */
+CF_EXPORT int cf_compute_batch_periodic_hvp(cf_handle* h, int32_t nconf, const double* pos_dev,
+                                            const double* boxes_host, int32_t nvec, const double* vec_dev,
+                                            double* out_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_periodic_hvp_host(cf_handle* h, int32_t nconf, const double* pos_host,
+                                                 const double* boxes_host, int32_t nvec, const double* vec_host,
+                                                 double* out_host);
 /* cap on the conformations evaluated per pass (bounds the batch workspace); 0 = automatic: as many
  * as keep the workspace (per conformation q[N], the flux slots, dq/dx, dE/dq[N], F[3N], e[N]; a
  * periodic batch also the phase tables, 4 doubles per [N][kmax_x + kmax_y + kmax_z] entry, and 3
@@ -626,7 +688,9 @@ CF_EXPORT int cf_compute_batch_hvp_host(cf_handle* h, int32_t nconf, const doubl
  * per conformation the doubles of cf_compute_batch, per (conformation, direction) S + 3 D + 3 N more
  * (S charge slots: 2 per bond, 3 per angle or water; D dq/dx entries: 4 per bond, 9 per angle or
  * water); the limit caps its conformations, and a conformation whose nvec directions alone exceed
- * 256 MiB or 65535 takes its directions in several passes.  A
+ * 256 MiB or 65535 takes its directions in several passes.  cf_compute_batch_periodic_hvp: the same
+ * rules with, per conformation, the doubles of cf_compute_batch_periodic and, per (conformation,
+ * direction), S + 3 D + 3 N and 2 more per k-vector.  A
  * larger batch runs as consecutive passes.  Applies to every batch form; cf_get_batch_stats counts
  * them all (a VJP call with all cotangents NULL counts its call and conformations, and no pass). */
 CF_EXPORT int cf_set_batch_limit(cf_handle* h, int32_t max_conformations);

@@ -6,6 +6,7 @@
 // differentiation of the very expressions flux_term evaluates, so the three term kinds need no
 // hand-written second derivatives.  cf_flux.h's bodies are not touched (the forward kernels keep
 // their code objects); with T = double this is flux_term's arithmetic, operation for operation.
+// flux_term_pbc below is the periodic branch in the same form (cf_kernels_batch_pbc_hvp.hip).
 #pragma once
 
 #include "cf_flux.h"
@@ -99,6 +100,85 @@ __device__ __forceinline__ void flux_term_nopbc(int type, const double* __restri
         T d12[3], d13[3], d23[3];
 #pragma unroll
         for (int j = 0; j < 3; j++) { d12[j] = x2[j] - x1[j]; d13[j] = x3[j] - x1[j]; d23[j] = x3[j] - x2[j]; }
+        const T r12 = num_sqrt(num_dot(d12, d12)), r13 = num_sqrt(num_dot(d13, d13)), r23 = num_sqrt(num_dot(d23, d23));
+        const double k1 = p[0], k2 = p[1], kub = p[2], b0 = p[3], ub0 = p[4];
+        const T dq2 = k1 * (r12 - b0) + k2 * (r13 - b0) + kub * (r23 - ub0);
+        const T dq3 = k1 * (r13 - b0) + k2 * (r12 - b0) + kub * (r23 - ub0);
+        dq[0] = -dq2 - dq3; dq[1] = dq2; dq[2] = dq3;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const T n12 = d12[j] / r12, n13 = d13[j] / r13, n23 = d23[j] / r23;
+            const T a12k1 = k1 * n12, a12k2 = k2 * n12, a13k1 = k1 * n13, a13k2 = k2 * n13, ub = kub * n23;
+            out(0 + j, a12k1 + a12k2 + a13k1 + a13k2);
+            out(3 + j, -a12k1 - a12k2 + 2.0 * ub);
+            out(6 + j, -a13k2 - a13k1 - 2.0 * ub);
+            out(9 + j, -a12k1 - a13k2);
+            out(12 + j, a12k1 - ub);
+            out(15 + j, a13k2 + ub);
+            out(18 + j, -a12k2 - a13k1);
+            out(21 + j, a12k2 - ub);
+            out(24 + j, a13k1 + ub);
+        }
+    }
+}
+
+// delta_r (cf_pair.h: b - a, minimum image in the reduced box L, T) under one name for both number
+// types.  The image shift is piecewise constant in the positions, so a Dual's value is delta_r of
+// the values and its tangent the plain difference of the tangents.
+__device__ __forceinline__ void num_delta(const double a[3], const double b[3], double3 L, double3 T, double out[3]) {
+    const double3 d = delta_r(make_double3(a[0], a[1], a[2]), make_double3(b[0], b[1], b[2]), L, 1, T);
+    out[0] = d.x; out[1] = d.y; out[2] = d.z;
+}
+__device__ __forceinline__ void num_delta(const Dual a[3], const Dual b[3], double3 L, double3 T, Dual out[3]) {
+    const double3 d = delta_r(make_double3(a[0].v, a[1].v, a[2].v), make_double3(b[0].v, b[1].v, b[2].v), L, 1, T);
+    out[0] = Dual(d.x, b[0].d - a[0].d); out[1] = Dual(d.y, b[1].d - a[1].d); out[2] = Dual(d.z, b[2].d - a[2].d);
+}
+
+// The periodic branch of flux_term (pbc = 1) over a number type T: flux_term_nopbc with every
+// difference vector the minimum image in the box (L, T), the delta_r calls flux_term makes, in its
+// order and with its arguments.  Arguments, dq and out as flux_term_nopbc.  A restatement of its own
+// (cf_kernels_batch_pbc_hvp.hip): flux_term_nopbc and the kernels that instantiate it stay as they are.
+template <class T, class Out>
+__device__ __forceinline__ void flux_term_pbc(int type, const double* __restrict__ p, const T x1[3], const T x2[3],
+                                              const T x3[3], double3 L, double3 Tb, T dq[3], Out&& out) {
+    if (type == 0) {
+        T d[3];
+        num_delta(x1, x2, L, Tb, d);
+        const T r = num_sqrt(num_dot(d, d));
+        const double k = p[0];
+        const T q = k * (r - p[1]);
+        dq[0] = q; dq[1] = -q; dq[2] = T(0.0);
+        const T c = k / r;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const T v = c * d[j];
+            out(j, -v); out(3 + j, v); out(6 + j, v); out(9 + j, -v);
+        }
+    } else if (type == 1) {
+        T d21[3], d23[3], d13[3];
+        num_delta(x2, x1, L, Tb, d21); num_delta(x2, x3, L, Tb, d23); num_delta(x1, x3, L, Tb, d13);
+        const T r21_2 = num_dot(d21, d21), r23_2 = num_dot(d23, d23), r13_2 = num_dot(d13, d13);
+        const T r21 = num_sqrt(r21_2), r23 = num_sqrt(r23_2);
+        const T cost = (r23_2 + r21_2 - r13_2) / 2.0 / r21 / r23;
+        const double k = p[0];
+        const T q = k * (num_acos(cost) - p[1]);
+        dq[0] = q; dq[1] = -2.0 * q; dq[2] = q;
+        const T inv_s = 1.0 / num_sqrt(1.0 - cost * cost);
+        const T c1 = k * (1.0 / r21 / r23) * inv_s;
+        const T c21 = k * cost * inv_s / r21_2;
+        const T c23 = k * cost * inv_s / r23_2;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const T v1 = -c1 * d23[j] + c21 * d21[j];
+            const T v3 = -c1 * d21[j] + c23 * d23[j];
+            const T v2 = -v1 - v3;
+            out(j, v1); out(3 + j, v2); out(6 + j, v3);
+            out(9 + j, -2.0 * v1); out(12 + j, -2.0 * v2); out(15 + j, -2.0 * v3);
+            out(18 + j, v1); out(21 + j, v2); out(24 + j, v3);
+        }
+    } else {
+        T d12[3], d13[3], d23[3];
+        num_delta(x1, x2, L, Tb, d12); num_delta(x1, x3, L, Tb, d13); num_delta(x2, x3, L, Tb, d23);
         const T r12 = num_sqrt(num_dot(d12, d12)), r13 = num_sqrt(num_dot(d13, d13)), r23 = num_sqrt(num_dot(d23, d23));
         const double k1 = p[0], k2 = p[1], kub = p[2], b0 = p[3], ub0 = p[4];
         const T dq2 = k1 * (r12 - b0) + k2 * (r13 - b0) + kub * (r23 - ub0);

@@ -445,6 +445,29 @@ void batch_hvp_carve(const Handle& h, double* base, int cap, BatchHvpWs& w);
 void launch_batch_hvp(Handle& h, const BatchWs& w, const BatchHvpWs& hw, int nconf, int kv, const double* pos,
                       const double* vec, long vstride, double* out);
 
+// Hessian-vector products of the periodic batch (cf_kernels_batch_pbc_hvp.hip,
+// cf_compute_batch_periodic_hvp): the extra workspace of one pass beside BatchPbcWs, one row per
+// (conformation, direction) of the pass, carved from one allocation of cap *
+// batch_pbc_hvp_doubles_per_row doubles (the double2 array first: 16-B aligned)
+struct BatchPbcHvpWs {
+    double* base = nullptr;
+    int cap = 0;                // rows the arrays hold
+    double2* coefd = nullptr;   // [cap][khalf] 2 c eak (Re Sdot, Im Sdot) along the direction
+    double* dslot = nullptr;    // [cap][S] tangents of the charge slots
+    double* ddot = nullptr;     // [cap][D * 3] tangent of dq/dx
+    double* qdot = nullptr;     // [cap][N] tangent of the charges
+    double* gdot = nullptr;     // [cap][N] tangent of dE/dq
+    double* g = nullptr;        // [cap][N] dE/dq, a row per CONFORMATION of the pass (never more than rows)
+};
+size_t batch_pbc_hvp_doubles_per_row(const Handle& h);
+void batch_pbc_hvp_carve(const Handle& h, double* base, int cap, BatchPbcHvpWs& w);
+int batch_pbc_hvp_chunk();      // directions a block of the pair / k-space kernels carries (build-time)
+// one pass of nconf <= w.cap conformations x kv directions (nconf * kv <= min(hw.cap, kBatchMaxPass)
+// rows) on h.stream: at most nine launches.  boxes: device, [nconf][8] as launch_batch_pbc; pos, vec,
+// vstride and out as launch_batch_hvp; out overwritten
+void launch_batch_pbc_hvp(Handle& h, const BatchPbcWs& w, const BatchPbcHvpWs& hw, int nconf, int kv, const double* pos,
+                          const double* boxes, const double* vec, long vstride, double* out);
+
 void check_hip(hipError_t e, const char* what);
 
 // ---- fp64 math helpers shared by the pair and grid kernels -------------------------

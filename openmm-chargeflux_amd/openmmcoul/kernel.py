@@ -537,7 +537,7 @@ class HipCalcCoulForceKernel:
         _cabi.check(self._lib.cf_compute_batch_dipole_vjp(self._h, nconf, ptr(positions), ptr(dipole_bar),
                                                           ptr(apt_bar), ptr(grad)), self._lib)
 
-    # Hessian-vector products of the non-periodic batch (cf_compute_batch_hvp) --------------------------
+    # Hessian-vector products of the batch (cf_compute_batch_hvp; boxes=: cf_compute_batch_periodic_hvp) --
     def _check_hvp_vectors(self, vectors, nconf, module, kind):
         if not isinstance(vectors, kind):
             raise ValueError(f"vectors must be a float64 {kind.__name__} of shape (B, K, N, 3)")
@@ -548,23 +548,32 @@ class HipCalcCoulForceKernel:
             raise ValueError(f"vectors holds {shape[0]} conformations, positions {nconf}")
         return shape[1]
 
-    def execute_batch_hvp_host(self, positions, vectors):
+    def execute_batch_hvp_host(self, positions, vectors, *, boxes=None):
         """Hessian-vector products of B conformations (cf_compute_batch_hvp_host; non-periodic
         systems).  positions (B,N,3) in nm, vectors (B,K,N,3): C-contiguous float64 numpy arrays, K
         directions per conformation.  Returns (B,K,N,3): H(x_b) v_bk, with H = d2E/dxdx of the energy
-        execute_batch_host returns (kJ/mol/nm^2 for v in nm)."""
+        execute_batch_host returns (kJ/mol/nm^2 for v in nm).
+        boxes (periodic systems, cf_compute_batch_periodic_hvp_host): as execute_batch_host --
+        float64 numpy (B,3,3), one box per conformation, or (3,3) for all of them; H at fixed box."""
         if not isinstance(positions, np.ndarray):
             raise ValueError("positions must be a numpy array of shape (B, N, 3)")
         nconf = self._check_batch_array(positions, "positions", (self._n, 3))
         nvec = self._check_hvp_vectors(vectors, nconf, np, np.ndarray)
         out = np.zeros((nconf, nvec, self._n, 3))
+        if boxes is not None:
+            b = self._batch_boxes(boxes, nconf)
+            _cabi.check(self._lib.cf_compute_batch_periodic_hvp_host(self._h, nconf, _dp(positions), _dp(b), nvec,
+                                                                     _dp(vectors), _dp(out)), self._lib)
+            return out
         _cabi.check(self._lib.cf_compute_batch_hvp_host(self._h, nconf, _dp(positions), nvec, _dp(vectors), _dp(out)),
                     self._lib)
         return out
 
-    def execute_batch_hvp_device(self, positions, vectors, out=None):
+    def execute_batch_hvp_device(self, positions, vectors, out=None, *, boxes=None):
         """The same on torch tensors (float64, on the kernel's device, contiguous): out (B,K,N,3) is
-        overwritten (created if None) and returned.  Asynchronous on the kernel's stream."""
+        overwritten (created if None) and returned.  Asynchronous on the kernel's stream.
+        boxes (periodic systems, cf_compute_batch_periodic_hvp): a numpy array in HOST memory here
+        too, read during the call."""
         import torch
         if not isinstance(positions, torch.Tensor):
             raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
@@ -576,20 +585,25 @@ class HipCalcCoulForceKernel:
               or self._check_batch_array(out, "out", (nvec, self._n, 3), torch) != nconf):
             raise ValueError("out must be a float64 torch tensor shaped like vectors")
         ptr = lambda t: C.c_void_p(t.data_ptr())
+        if boxes is not None:
+            b = self._batch_boxes(boxes, nconf)
+            _cabi.check(self._lib.cf_compute_batch_periodic_hvp(self._h, nconf, ptr(positions), _dp(b), nvec,
+                                                                ptr(vectors), ptr(out)), self._lib)
+            return out
         _cabi.check(self._lib.cf_compute_batch_hvp(self._h, nconf, ptr(positions), nvec, ptr(vectors), ptr(out)),
                     self._lib)
         return out
 
-    def hessians_host(self, positions, symmetrize=True):
+    def hessians_host(self, positions, symmetrize=True, *, boxes=None):
         """Full Hessians (B,3N,3N) of B conformations: one execute_batch_hvp_host call with the 3N unit
         vectors per conformation, symmetrised as (H + H^T) / 2 (symmetrize=False: the products as they
-        come, row k = H e_k)."""
+        come, row k = H e_k).  boxes: as execute_batch_hvp_host (periodic systems)."""
         if not isinstance(positions, np.ndarray):
             raise ValueError("positions must be a numpy array of shape (B, N, 3)")
         nconf = self._check_batch_array(positions, "positions", (self._n, 3))
         n3 = 3 * self._n
         units = np.ascontiguousarray(np.broadcast_to(np.eye(n3).reshape(n3, self._n, 3), (nconf, n3, self._n, 3)))
-        hess = self.execute_batch_hvp_host(positions, units).reshape(nconf, n3, n3)
+        hess = self.execute_batch_hvp_host(positions, units, boxes=boxes).reshape(nconf, n3, n3)
         return 0.5 * (hess + hess.transpose(0, 2, 1)) if symmetrize else hess
 
     def set_batch_limit(self, n: int):
