@@ -38,7 +38,8 @@ extern "C" {
                               cf_compute_batch_dipole_host, cf_compute_batch_dipole_vjp,
                               cf_compute_batch_dipole_vjp_host; cf_compute_batch_hvp,
                               cf_compute_batch_hvp_host; cf_compute_batch_periodic_hvp,
-                              cf_compute_batch_periodic_hvp_host */
+                              cf_compute_batch_periodic_hvp_host; cf_compute_batch_periodic_virial,
+                              cf_compute_batch_periodic_virial_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -669,7 +670,8 @@ CF_EXPORT int cf_compute_batch_hvp_host(cf_handle* h, int32_t nconf, const doubl
  * cf_set_timing), asynchronous.  cf_get_batch_stats counts the call, its nconf conformations and its
  * passes; cf_compute's state and diagnostics are not touched, and the forward periodic batch and both
  * periodic VJPs return the same bits before and after.  No guard bits.  Out of scope: the derivative
- * with respect to the box (stress, elastic constants) and of H with respect to the parameters.
+ * of H with respect to the box (elastic constants; the virial of a frame is
+ * cf_compute_batch_periodic_virial's) and with respect to the parameters.
  */
 CF_EXPORT int cf_compute_batch_periodic_hvp(cf_handle* h, int32_t nconf, const double* pos_dev,
                                             const double* boxes_host, int32_t nvec, const double* vec_dev,
@@ -678,6 +680,54 @@ CF_EXPORT int cf_compute_batch_periodic_hvp(cf_handle* h, int32_t nconf, const d
 CF_EXPORT int cf_compute_batch_periodic_hvp_host(cf_handle* h, int32_t nconf, const double* pos_host,
                                                  const double* boxes_host, int32_t nvec, const double* vec_host,
                                                  double* out_host);
+/*
+ * cf_compute_batch_periodic with the virial tensor of every frame: the third training and validation
+ * label of NVT / NPT frames beside energy and forces (pressure, cell relaxation, NPT density).
+ *   virial_dev [nconf][9] fp64, row-major 3 x 3 per conformation, OVERWRITTEN (kJ/mol)
+ *   virial[c] = -dE/d eps at eps = 0
+ * for the strain x_i -> x_i (I + eps), h -> h (I + eps) of the positions and the box h (rows a, b, c)
+ * together, at fixed alpha, kmax, cutoff, pair set and minimum-image shift of every pair (the "fixed
+ * images" convention of cf_compute_batch_periodic_hvp: no surface term for a pair exactly at the
+ * cutoff or at a face).  E is the energy of cf_compute_batch_periodic with ALL its parts -- self, erfc
+ * pairs and LJ within the cutoff, the erf correction of excluded pairs, the reciprocal sum -- whatever
+ * the CF_INCLUDE_* flags (as the VJP calls), and the charges follow the geometry.  The pressure
+ * beyond the kinetic part is tr(virial) / (3 V), the stress -virial / V.  Three parts, each symmetric;
+ * six sums are stored and mirrored, so virial[c] equals its transpose exactly:
+ *   pairs       1/2 sum_i sum_{j != i} s_ij d_ij (x) d_ij, d_ij the minimum image of x_i - x_j and
+ *               s_ij d_ij the force on i from j (erfc + LJ pair within the cutoff, erf correction of
+ *               an excluded pair at any distance)
+ *   reciprocal  sum_k ek_k [delta_ab - 2 k_a k_b (1 / k^2 + 1 / (4 alpha^2))] over the half-space k set,
+ *               ek_k the k-vector's energy term, k = 2 pi n / L from the box diagonals
+ *   charges     -sum_a g_a dq_a/d eps_ab,  dq_a/d eps_ab = sum over the flux terms and their atoms b of
+ *               (x_b - x_anchor)_a (dq_a/dx_b)_b by the term's own minimum image; g = dE/dq complete
+ *               (the self term enters here only)
+ * Forces, energy and charges: arguments, flags, asynchrony, pass splitting (the same automatic pass
+ * sizes: the tensor sums' scratch, 6 doubles per 64 atoms and per 256 flux terms of a conformation, is
+ * allocated apart), statistics, errors and states are cf_compute_batch_periodic's, and forces_dev,
+ * energy_dev and charges_dev receive bitwise what that call writes.  virial_dev == NULL: the call IS
+ * cf_compute_batch_periodic.  A pass is at most nine kernel launches whatever nconf (the forward
+ * call's with the pair kernel carrying the six sums in the same sweep, then the charge-response
+ * kernel and the closing reduction).  fp64, no atomics; every sum's order depends only on N, the
+ * topology and kmax: a frame's tensor is bitwise the same alone, at any position of any batch, under
+ * any pass size and in the host and the device form.
+ * TRICLINIC frames are rejected: the forward call's reciprocal part reads only the box diagonals,
+ * also for a triclinic box, and that function of (x, h) has no strain tensor that is invariant under
+ * translation.  A box with a non-zero off-diagonal gives CF_ERR_INVALID with a message naming the
+ * conformation index, before anything is launched or counted, as a bad box does.  A non-periodic
+ * handle gives CF_ERR_INVALID, world_size > 1 and a call between cf_compute_begin and _end
+ * CF_ERR_STATE; a NULL handle is rejected without touching a device.
+ * Out of scope: the parameter gradients of the virial (the VJP a stress-matching loss needs) and a
+ * torch layer; triclinic frames; non-periodic handles; the kinetic part of the pressure; long-range
+ * LJ corrections (the forward call has none).
+ */
+CF_EXPORT int cf_compute_batch_periodic_virial(cf_handle* h, int32_t nconf, const double* pos_dev,
+                                               const double* boxes_host, int flags, double* forces_dev,
+                                               double* energy_dev, double* charges_dev, double* virial_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H); forces_host ADDED to, virial_host
+ * [nconf][9] overwritten (NULL: cf_compute_batch_periodic_host) */
+CF_EXPORT int cf_compute_batch_periodic_virial_host(cf_handle* h, int32_t nconf, const double* pos_host,
+                                                    const double* boxes_host, int flags, double* forces_host,
+                                                    double* energy_host, double* charges_host, double* virial_host);
 /* cap on the conformations evaluated per pass (bounds the batch workspace); 0 = automatic: as many
  * as keep the workspace (per conformation q[N], the flux slots, dq/dx, dE/dq[N], F[3N], e[N]; a
  * periodic batch also the phase tables, 4 doubles per [N][kmax_x + kmax_y + kmax_z] entry, and 3
@@ -690,7 +740,8 @@ CF_EXPORT int cf_compute_batch_periodic_hvp_host(cf_handle* h, int32_t nconf, co
  * water); the limit caps its conformations, and a conformation whose nvec directions alone exceed
  * 256 MiB or 65535 takes its directions in several passes.  cf_compute_batch_periodic_hvp: the same
  * rules with, per conformation, the doubles of cf_compute_batch_periodic and, per (conformation,
- * direction), S + 3 D + 3 N and 2 more per k-vector.  A
+ * direction), S + 3 D + 3 N and 2 more per k-vector.  cf_compute_batch_periodic_virial: the
+ * doubles of cf_compute_batch_periodic (its scratch is not counted).  A
  * larger batch runs as consecutive passes.  Applies to every batch form; cf_get_batch_stats counts
  * them all (a VJP call with all cotangents NULL counts its call and conformations, and no pass). */
 CF_EXPORT int cf_set_batch_limit(cf_handle* h, int32_t max_conformations);

@@ -98,6 +98,11 @@ struct cf_handle {
     // cf_compute_batch_periodic_hvp: the extra workspace beside `batch_pbc`, a row per (conformation,
     // direction) of a pass (in H->allocs); its host form stages through batch_hvp_stage
     cf::BatchPbcHvpWs batch_pbc_hvp;
+    // cf_compute_batch_periodic_virial: the tensor sums' scratch beside `batch_pbc` and the host form's
+    // staging of the tensors [confs][9] (its other arrays go through batch_stage); both in H->allocs
+    cf::BatchPbcVirialWs batch_pbc_virial;
+    double* batch_virial_stage = nullptr;
+    int64_t batch_virial_stage_confs = 0;
 };
 
 namespace {
@@ -1988,45 +1993,143 @@ CF_EXPORT int cf_compute_batch_periodic(cf_handle* H, int32_t nconf, const doubl
     });
 }
 
+// The host forms of the periodic forward call and of the virial call: positions up through the
+// handle's staging buffer, `call(pos, frc, ene, chg)` on the device copies (a null for every output
+// that is not wanted; it may queue further copies on the stream), the results back; synchronous.
+using BatchPeriodicCall = std::function<int(const double*, double*, double*, double*)>;
+static void batch_periodic_staged(cf_handle* H, int32_t nconf, const double* pos_host, int flags, double* forces_host,
+                                  double* energy_host, double* charges_host, const BatchPeriodicCall& call) {
+    cf::Handle& h = H->h;
+    check_hip(hipSetDevice(h.device), "hipSetDevice");
+    const size_t n = (size_t)h.n, B = (size_t)nconf;
+    if (nconf > H->batch_stage_confs) {
+        double* old = H->batch_stage;
+        H->batch_stage = nullptr; H->batch_stage_confs = 0;
+        dfree(H, old);
+        H->batch_stage = dalloc<double>(H, B * (3 * n + 3 * n + n + 1));
+        H->batch_stage_confs = nconf;
+    }
+    double* pos = H->batch_stage;
+    double* frc = pos + 3 * n * B;
+    double* chg = frc + 3 * n * B;
+    double* ene = chg + n * B;
+    const bool fw = forces_host && (flags & CF_INCLUDE_FORCES);
+    check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+              "H2D positions");
+    if (fw) check_hip(hipMemsetAsync(frc, 0, sizeof(double) * 3 * n * B, h.stream), "memset forces");
+    const int rc = call(pos, fw ? frc : nullptr, energy_host ? ene : nullptr, charges_host ? chg : nullptr);
+    if (rc != CF_OK) throw CfError(rc, g_err);
+    std::vector<double> f(fw ? 3 * n * B : 0);
+    if (fw)
+        check_hip(hipMemcpyAsync(f.data(), frc, sizeof(double) * 3 * n * B, hipMemcpyDeviceToHost, h.stream),
+                  "D2H forces");
+    if (energy_host)
+        check_hip(hipMemcpyAsync(energy_host, ene, sizeof(double) * B, hipMemcpyDeviceToHost, h.stream), "D2H energies");
+    if (charges_host)
+        check_hip(hipMemcpyAsync(charges_host, chg, sizeof(double) * n * B, hipMemcpyDeviceToHost, h.stream),
+                  "D2H charges");
+    check_hip(hipStreamSynchronize(h.stream), "sync");
+    if (fw)
+        for (size_t k = 0; k < f.size(); k++) forces_host[k] += f[k];
+}
+
 CF_EXPORT int cf_compute_batch_periodic_host(cf_handle* H, int32_t nconf, const double* pos_host,
                                              const double* boxes_host, int flags, double* forces_host,
                                              double* energy_host, double* charges_host) {
     return guarded([&] {
         batch_periodic_precheck(H, nconf, pos_host, boxes_host, "cf_compute_batch_periodic_host");
         if (nconf == 0) return;
+        batch_periodic_staged(H, nconf, pos_host, flags, forces_host, energy_host, charges_host,
+                              [&](const double* pos, double* frc, double* ene, double* chg) {
+                                  return cf_compute_batch_periodic(H, nconf, pos, boxes_host, flags, frc, ene, chg);
+                              });
+    });
+}
+
+// ---- virial tensors of the periodic batch (cf_kernels_batch_pbc_virial.hip) -------------------------
+// Everything that can refuse the call, before anything is launched, staged or counted: the forward
+// call's checks, then every box orthorhombic (the reciprocal part reads only the box diagonals, also
+// for a triclinic box: that function of positions and box has no translation-invariant strain tensor).
+static void batch_periodic_virial_precheck(cf_handle* H, int32_t nconf, const double* pos, const double* boxes_host,
+                                           const char* name) {
+    batch_periodic_precheck(H, nconf, pos, boxes_host, name);
+    for (int32_t c = 0; c < nconf; c++) {
+        const double* b = boxes_host + 9 * (size_t)c;
+        if (b[3] != 0.0 || b[6] != 0.0 || b[7] != 0.0)
+            fail(CF_ERR_INVALID, std::string(name) + ": box of conformation " + std::to_string(c) +
+                                     " is triclinic (the virial is defined for orthorhombic boxes only)");
+    }
+}
+
+CF_EXPORT int cf_compute_batch_periodic_virial(cf_handle* H, int32_t nconf, const double* pos_dev,
+                                               const double* boxes_host, int flags, double* forces_dev,
+                                               double* energy_dev, double* charges_dev, double* virial_dev) {
+    if (!virial_dev) return cf_compute_batch_periodic(H, nconf, pos_dev, boxes_host, flags, forces_dev, energy_dev, charges_dev);
+    return guarded([&] {
+        batch_periodic_virial_precheck(H, nconf, pos_dev, boxes_host, "cf_compute_batch_periodic_virial");
+        if (nconf == 0) return;
         cf::Handle& h = H->h;
         check_hip(hipSetDevice(h.device), "hipSetDevice");
-        const size_t n = (size_t)h.n, B = (size_t)nconf;
-        if (nconf > H->batch_stage_confs) {
-            double* old = H->batch_stage;
-            H->batch_stage = nullptr; H->batch_stage_confs = 0;
+        const int pass = batch_pbc_pass_size(H, nconf);   // the forward call's passes: the scratch is sized apart
+        if (pass > H->batch_pbc.cap) {   // first call or growth: allocates (and so synchronises)
+            double* old = H->batch_pbc.base;
+            H->batch_pbc = cf::BatchPbcWs();
             dfree(H, old);
-            H->batch_stage = dalloc<double>(H, B * (3 * n + 3 * n + n + 1));
-            H->batch_stage_confs = nconf;
+            double* base = dalloc<double>(H, cf::batch_pbc_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_pbc_carve(h, base, pass, H->batch_pbc);
         }
-        double* pos = H->batch_stage;
-        double* frc = pos + 3 * n * B;
-        double* chg = frc + 3 * n * B;
-        double* ene = chg + n * B;
-        const bool fw = forces_host && (flags & CF_INCLUDE_FORCES);
-        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
-                  "H2D positions");
-        if (fw) check_hip(hipMemsetAsync(frc, 0, sizeof(double) * 3 * n * B, h.stream), "memset forces");
-        const int rc = cf_compute_batch_periodic(H, nconf, pos, boxes_host, flags, fw ? frc : nullptr,
-                                                 energy_host ? ene : nullptr, charges_host ? chg : nullptr);
-        if (rc != CF_OK) throw CfError(rc, g_err);
-        std::vector<double> f(fw ? 3 * n * B : 0);
-        if (fw)
-            check_hip(hipMemcpyAsync(f.data(), frc, sizeof(double) * 3 * n * B, hipMemcpyDeviceToHost, h.stream),
-                      "D2H forces");
-        if (energy_host)
-            check_hip(hipMemcpyAsync(energy_host, ene, sizeof(double) * B, hipMemcpyDeviceToHost, h.stream), "D2H energies");
-        if (charges_host)
-            check_hip(hipMemcpyAsync(charges_host, chg, sizeof(double) * n * B, hipMemcpyDeviceToHost, h.stream),
-                      "D2H charges");
-        check_hip(hipStreamSynchronize(h.stream), "sync");
-        if (fw)
-            for (size_t k = 0; k < f.size(); k++) forces_host[k] += f[k];
+        if (pass > H->batch_pbc_virial.cap) {
+            double* old = H->batch_pbc_virial.base;
+            H->batch_pbc_virial = cf::BatchPbcVirialWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_pbc_virial_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_pbc_virial_carve(h, base, pass, H->batch_pbc_virial);
+        }
+        batch_boxes_upload(H, nconf, boxes_host);
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events (as cf_compute_batch_periodic)
+        const size_t n = (size_t)h.n;
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            cf::launch_batch_pbc_virial(h, H->batch_pbc, H->batch_pbc_virial, m, pos_dev + 3 * n * c0,
+                                        H->batch_boxes_dev + 8 * (size_t)c0, flags,
+                                        forces_dev ? forces_dev + 3 * n * c0 : nullptr,
+                                        energy_dev ? energy_dev + c0 : nullptr,
+                                        charges_dev ? charges_dev + n * c0 : nullptr, virial_dev + 9 * (size_t)c0);
+            H->batch_passes++;
+        }
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        launch_check(h, "compute_batch_periodic_virial");
+    });
+}
+
+CF_EXPORT int cf_compute_batch_periodic_virial_host(cf_handle* H, int32_t nconf, const double* pos_host,
+                                                    const double* boxes_host, int flags, double* forces_host,
+                                                    double* energy_host, double* charges_host, double* virial_host) {
+    if (!virial_host)
+        return cf_compute_batch_periodic_host(H, nconf, pos_host, boxes_host, flags, forces_host, energy_host, charges_host);
+    return guarded([&] {
+        batch_periodic_virial_precheck(H, nconf, pos_host, boxes_host, "cf_compute_batch_periodic_virial_host");
+        if (nconf == 0) return;
+        if (nconf > H->batch_virial_stage_confs) {
+            check_hip(hipSetDevice(H->h.device), "hipSetDevice");
+            double* old = H->batch_virial_stage;
+            H->batch_virial_stage = nullptr; H->batch_virial_stage_confs = 0;
+            dfree(H, old);
+            H->batch_virial_stage = dalloc<double>(H, 9 * (size_t)nconf);
+            H->batch_virial_stage_confs = nconf;
+        }
+        batch_periodic_staged(H, nconf, pos_host, flags, forces_host, energy_host, charges_host,
+                              [&](const double* pos, double* frc, double* ene, double* chg) {
+                                  const int rc = cf_compute_batch_periodic_virial(H, nconf, pos, boxes_host, flags, frc,
+                                                                                  ene, chg, H->batch_virial_stage);
+                                  if (rc == CF_OK)
+                                      check_hip(hipMemcpyAsync(virial_host, H->batch_virial_stage,
+                                                               sizeof(double) * 9 * (size_t)nconf, hipMemcpyDeviceToHost,
+                                                               H->h.stream), "D2H virials");
+                                  return rc;
+                              });
     });
 }
 

@@ -385,6 +385,31 @@ void launch_batch_pbc(Handle& h, const BatchPbcWs& w, int nconf, const double* p
 void launch_batch_pbc_flux_charges(Handle& h, const BatchPbcWs& w, int nconf, const double* pos, const double* boxes,
                                    double* charges);
 void launch_batch_pbc_tables(Handle& h, const BatchPbcWs& w, int nconf, const double* pos, const double* boxes);
+// its k-space and closing launches, shared with the virial call: k_bp_sfac (coef, ek), k_bp_recip
+// (completes dedq and f_part) and k_bp_assemble (forces ADDED to, energy written; each may be null)
+void launch_batch_pbc_sfac(Handle& h, const BatchPbcWs& w, int nconf, const double* boxes);
+void launch_batch_pbc_recip(Handle& h, const BatchPbcWs& w, int nconf, const double* boxes);
+void launch_batch_pbc_assemble(Handle& h, const BatchPbcWs& w, int nconf, double* forces, double* energy,
+                               int include_recip);
+
+// virial tensors of the periodic batch (cf_kernels_batch_pbc_virial.hip,
+// cf_compute_batch_periodic_virial): the scratch of one pass beside BatchPbcWs, one 6-vector
+// (xx, xy, xz, yy, yz, zz) per (conformation, i-block of the pair kernel) and per (conformation,
+// block of the flux kernel), carved from one allocation of cap * batch_pbc_virial_doubles_per_conf
+struct BatchPbcVirialWs {
+    double* base = nullptr;
+    int cap = 0;                // conformations the arrays hold
+    double* pair = nullptr;     // [cap][ceil(N / 64)][6]
+    double* flux = nullptr;     // [cap][ceil(nterms / 256)][6]
+};
+size_t batch_pbc_virial_doubles_per_conf(const Handle& h);
+void batch_pbc_virial_carve(const Handle& h, double* base, int cap, BatchPbcVirialWs& w);
+// one pass of nconf <= min(w.cap, vw.cap) conformations on h.stream: at most nine launches, whatever
+// nconf.  Arguments as launch_batch_pbc; forces, energy and charges get its bits.  virial [nconf][9]
+// overwritten.  Every box orthorhombic (the caller has checked)
+void launch_batch_pbc_virial(Handle& h, const BatchPbcWs& w, const BatchPbcVirialWs& vw, int nconf, const double* pos,
+                             const double* boxes, int flags, double* forces, double* energy, double* charges,
+                             double* virial);
 
 // parameter gradients of the periodic batch (cf_kernels_batch_pbc_grad.hip,
 // cf_compute_batch_periodic_vjp): the extra workspace of one pass beside BatchPbcWs, carved from one

@@ -350,32 +350,42 @@ void launch_batch_pbc_tables(Handle& h, const BatchPbcWs& w, int nconf, const do
                        w.tab, w.tab_t);
 }
 
+// the k-space and closing launches of a pass, shared with the virial call (cf_kernels_batch_pbc_virial.hip)
+void launch_batch_pbc_sfac(Handle& h, const BatchPbcWs& w, int nconf, const double* boxes) {
+    const long khalf = (long)h.khalf;
+    hipLaunchKernelGGL(k_bp_sfac, dim3(nblk(khalf, 256), nconf), dim3(256), 0, h.stream, h.n, h.kmax[0], h.kmax[1],
+                       h.kmax[2], khalf, h.ke, 1.0 / (h.alpha * h.alpha), boxes, w.q, w.tab, w.coef, w.ek);
+}
+
+void launch_batch_pbc_recip(Handle& h, const BatchPbcWs& w, int nconf, const double* boxes) {
+    hipLaunchKernelGGL(k_bp_recip, dim3(nblk(h.n, 64), nconf), dim3(256), 0, h.stream, h.n, h.kmax[0], h.kmax[1],
+                       h.kmax[2], (long)h.khalf, boxes, w.q, w.tab_t, w.coef, w.dedq, w.f_part);
+}
+
+void launch_batch_pbc_assemble(Handle& h, const BatchPbcWs& w, int nconf, double* forces, double* energy,
+                               int include_recip) {
+    hipLaunchKernelGGL(k_bp_assemble, dim3(nblk(h.n, 256), nconf), dim3(256), 0, h.stream, h.n, 3L * h.nd,
+                       (long)h.khalf, h.ccsr_start, h.ccsr_ent, w.dedq, w.dqdx, w.f_part, forces, w.e_atom, w.ek,
+                       include_recip, energy);
+}
+
 void launch_batch_pbc(Handle& h, const BatchPbcWs& w, int nconf, const double* pos, const double* boxes, int flags,
                       double* forces, double* energy, double* charges) {
     if (nconf <= 0 || nconf > w.cap || nconf > kBatchMaxPass) throw std::invalid_argument("launch_batch_pbc: pass size");
     const int n = h.n;
-    const int KX = h.kmax[0], KY = h.kmax[1], KZ = h.kmax[2];
-    const long khalf = (long)h.khalf;
     const bool do_f = (flags & CF_INCLUDE_FORCES) && forces;
     const bool do_er = (flags & CF_INCLUDE_ENERGY) && energy;   // the reciprocal energy (the rest: whatever the flags)
-    const long nd3 = 3L * h.nd;
     launch_batch_pbc_flux_charges(h, w, nconf, pos, boxes, charges);
     if (do_f || do_er) {
         launch_batch_pbc_tables(h, w, nconf, pos, boxes);
-        hipLaunchKernelGGL(k_bp_sfac, dim3(nblk(khalf, 256), nconf), dim3(256), 0, h.stream, n, KX, KY, KZ, khalf, h.ke,
-                           1.0 / (h.alpha * h.alpha), boxes, w.q, w.tab, w.coef, w.ek);
+        launch_batch_pbc_sfac(h, w, nconf, boxes);
     }
     if (do_f || energy)
         hipLaunchKernelGGL(k_bp_pairs, dim3(nblk(n, kPbcI), nconf), dim3(kPbcJ), 0, h.stream, n, do_f ? 1 : 0, h.ke,
                            h.alpha, h.cutoff * h.cutoff, h.erfc_scale, h.erfc_tab, boxes, pos, w.q, h.lj, h.ex_start,
                            h.ex_list, w.dedq, w.f_part, w.e_atom);
-    if (do_f)
-        hipLaunchKernelGGL(k_bp_recip, dim3(nblk(n, 64), nconf), dim3(256), 0, h.stream, n, KX, KY, KZ, khalf, boxes, w.q,
-                           w.tab_t, w.coef, w.dedq, w.f_part);
-    if (do_f || energy)
-        hipLaunchKernelGGL(k_bp_assemble, dim3(nblk(n, 256), nconf), dim3(256), 0, h.stream, n, nd3, khalf,
-                           h.ccsr_start, h.ccsr_ent, w.dedq, w.dqdx, w.f_part, do_f ? forces : nullptr, w.e_atom, w.ek,
-                           do_er ? 1 : 0, energy);
+    if (do_f) launch_batch_pbc_recip(h, w, nconf, boxes);
+    if (do_f || energy) launch_batch_pbc_assemble(h, w, nconf, do_f ? forces : nullptr, energy, do_er ? 1 : 0);
 }
 
 }  // namespace cf

@@ -354,6 +354,44 @@ class HipCalcCoulForceKernel:
                                                self._flags(includeForces, includeEnergy), ptr(forces),
                                                ptr(energies), ptr(charges)), self._lib)
 
+    # the periodic batch with the virial tensor of every frame (cf_compute_batch_periodic_virial) -------
+    def execute_batch_virial_host(self, positions, boxes, includeForces=True, includeEnergy=True):
+        """B periodic frames with their virial tensors (cf_compute_batch_periodic_virial_host):
+        positions (B,N,3) float64 C-contiguous numpy, boxes as execute_batch_host (orthorhombic).
+        Returns (energies (B,), forces (B,N,3), charges (B,N), virials (B,3,3)); energies, forces
+        and charges are execute_batch_host's bits, virials[c] = -dE/d(strain) in kJ/mol, symmetric."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        b = self._batch_boxes(boxes, nconf)
+        forces, energies = np.zeros((nconf, self._n, 3)), np.zeros(nconf)
+        charges, virials = np.zeros((nconf, self._n)), np.zeros((nconf, 3, 3))
+        _cabi.check(self._lib.cf_compute_batch_periodic_virial_host(
+            self._h, nconf, _dp(positions), _dp(b), self._flags(includeForces, includeEnergy), _dp(forces),
+            _dp(energies), _dp(charges), _dp(virials)), self._lib)
+        return energies, forces, charges, virials
+
+    def execute_batch_virial_device(self, positions, includeForces, includeEnergy, forces=None, energies=None,
+                                    charges=None, virials=None, *, boxes):
+        """The same on torch tensors, the conventions of execute_batch_device: forces (B,N,3) ADDED to,
+        energies (B,), charges (B,N) and virials (B,3,3) overwritten; each output may be None (without
+        virials the call is execute_batch_device's).  Asynchronous on the kernel's stream; boxes a numpy
+        array in HOST memory, read during the call."""
+        import torch
+        if not isinstance(positions, torch.Tensor):
+            raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
+        for t, name, trailing in ((forces, "forces", (self._n, 3)), (energies, "energies", ()),
+                                  (charges, "charges", (self._n,)), (virials, "virials", (3, 3))):
+            if t is not None and (not isinstance(t, torch.Tensor)
+                                  or self._check_batch_array(t, name, trailing, torch) != nconf):
+                raise ValueError(f"{name} must be a float64 torch tensor for {nconf} conformations")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _cabi.check(self._lib.cf_compute_batch_periodic_virial(
+            self._h, nconf, ptr(positions), _dp(self._batch_boxes(boxes, nconf)),
+            self._flags(includeForces, includeEnergy), ptr(forces), ptr(energies), ptr(charges), ptr(virials)),
+            self._lib)
+
     # parameter gradients of the batch (cf_compute_batch_vjp; boxes=: cf_compute_batch_periodic_vjp) --
     def param_counts(self):
         """(N, 2 * bonds, 2 * angles, 5 * waters): the lengths of the four parameter groups of a
