@@ -39,7 +39,8 @@ extern "C" {
                               cf_compute_batch_dipole_vjp_host; cf_compute_batch_hvp,
                               cf_compute_batch_hvp_host; cf_compute_batch_periodic_hvp,
                               cf_compute_batch_periodic_hvp_host; cf_compute_batch_periodic_virial,
-                              cf_compute_batch_periodic_virial_host */
+                              cf_compute_batch_periodic_virial_host; cf_compute_batch_periodic_virial_vjp,
+                              cf_compute_batch_periodic_virial_vjp_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -716,9 +717,9 @@ CF_EXPORT int cf_compute_batch_periodic_hvp_host(cf_handle* h, int32_t nconf, co
  * conformation index, before anything is launched or counted, as a bad box does.  A non-periodic
  * handle gives CF_ERR_INVALID, world_size > 1 and a call between cf_compute_begin and _end
  * CF_ERR_STATE; a NULL handle is rejected without touching a device.
- * Out of scope: the parameter gradients of the virial (the VJP a stress-matching loss needs) and a
- * torch layer; triclinic frames; non-periodic handles; the kinetic part of the pressure; long-range
- * LJ corrections (the forward call has none).
+ * Its parameter gradients: cf_compute_batch_periodic_virial_vjp, below.  Out of scope: triclinic
+ * frames; non-periodic handles; the kinetic part of the pressure; long-range LJ corrections (the
+ * forward call has none).
  */
 CF_EXPORT int cf_compute_batch_periodic_virial(cf_handle* h, int32_t nconf, const double* pos_dev,
                                                const double* boxes_host, int flags, double* forces_dev,
@@ -728,6 +729,47 @@ CF_EXPORT int cf_compute_batch_periodic_virial(cf_handle* h, int32_t nconf, cons
 CF_EXPORT int cf_compute_batch_periodic_virial_host(cf_handle* h, int32_t nconf, const double* pos_host,
                                                     const double* boxes_host, int flags, double* forces_host,
                                                     double* energy_host, double* charges_host, double* virial_host);
+/*
+ * Parameter gradients of the virial tensors: the reverse-mode product a stress-, pressure- or
+ * density-matching loss needs.  Per conformation, with the cotangent
+ *   virial_bar_dev [nconf][9] fp64, row-major 3 x 3 (NULL = zero),
+ * the scalar is L = virial_bar : virial, virial = cf_compute_batch_periodic_virial's tensor (the same
+ * convention: fixed images and pair set, orthorhombic frames, E with all its parts).  The tensor is
+ * symmetric, so only T = (virial_bar + virial_bar^T) / 2 enters: an antisymmetric cotangent gives exact
+ * zeros, a cotangent and its transpose the same bits.  L = -D_T E, the derivative along the strain
+ * x -> x (I + t T), h -> h (I + t T): every minimum-image vector d (pairs and flux-term geometry) has the
+ * tangent d T (the image shift strains too), the phases k . x are invariant, and the reciprocal
+ * coefficients change through V and k^2.
+ *   grad_dev    [nconf][P]   dL/d(base charges, flux parameters), rows in cf_get_param_counts order
+ *   lj_grad_dev [nconf][2 N] dL/dsigma_i then dL/deps_i (cf_compute_batch_lj_vjp's layout and its
+ *                            convention: an atom with eps = 0 receives exactly 0 for both)
+ * Both are OVERWRITTEN, one row per conformation (not summed over them); either may be NULL.  Both
+ * NULL: the call and its conformations are counted, nothing is launched.  virial_bar_dev == NULL: the
+ * requested outputs are set to exact zeros (memset), counted, no pass.  Nothing divides by a
+ * parameter: a term with k = 0 is legal.
+ * A pass is at most nine kernel launches whatever nconf (flux terms, charges, phase tables, then the
+ * strain direction, charge tangents, structure factors, pairs, reciprocal part, term gradients); the LJ
+ * rows alone take two.  fp64, no atomics; every sum's order depends only on N, the topology and kmax,
+ * so a conformation's rows are bitwise the same alone, at any position of any batch, under any pass
+ * size, in the host and the device form and with or without the LJ output.
+ * Boxes, errors and states as cf_compute_batch_periodic_virial and cf_compute_batch_periodic_vjp:
+ * boxes_host is copied through the pinned buffer and is the caller's again on return; every box is
+ * checked before anything is launched or counted, a triclinic one gives CF_ERR_INVALID with a message
+ * naming the conformation; a non-periodic handle CF_ERR_INVALID; world_size > 1 or a call between
+ * cf_compute_begin and _end CF_ERR_STATE; NULL pos or boxes, nconf < 0 CF_ERR_INVALID; nconf = 0 is a
+ * no-op that counts nothing; a NULL handle is rejected without touching a device.  Eager launches on
+ * the handle's stream (never captured or replayed, not recorded by cf_set_timing), asynchronous;
+ * cf_compute's state and the other batch calls' results are not touched.  No guard bits.
+ * Out of scope: triclinic frames; position and box gradients of the virial; the kinetic pressure;
+ * long-range LJ corrections.
+ */
+CF_EXPORT int cf_compute_batch_periodic_virial_vjp(cf_handle* h, int32_t nconf, const double* pos_dev,
+                                                   const double* boxes_host, const double* virial_bar_dev,
+                                                   double* grad_dev, double* lj_grad_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_periodic_virial_vjp_host(cf_handle* h, int32_t nconf, const double* pos_host,
+                                                        const double* boxes_host, const double* virial_bar_host,
+                                                        double* grad_host, double* lj_grad_host);
 /* cap on the conformations evaluated per pass (bounds the batch workspace); 0 = automatic: as many
  * as keep the workspace (per conformation q[N], the flux slots, dq/dx, dE/dq[N], F[3N], e[N]; a
  * periodic batch also the phase tables, 4 doubles per [N][kmax_x + kmax_y + kmax_z] entry, and 3
@@ -741,7 +783,9 @@ CF_EXPORT int cf_compute_batch_periodic_virial_host(cf_handle* h, int32_t nconf,
  * 256 MiB or 65535 takes its directions in several passes.  cf_compute_batch_periodic_hvp: the same
  * rules with, per conformation, the doubles of cf_compute_batch_periodic and, per (conformation,
  * direction), S + 3 D + 3 N and 2 more per k-vector.  cf_compute_batch_periodic_virial: the
- * doubles of cf_compute_batch_periodic (its scratch is not counted).  A
+ * doubles of cf_compute_batch_periodic (its scratch is not counted).
+ * cf_compute_batch_periodic_virial_vjp: the doubles of cf_compute_batch_periodic and qdot[N], g[N],
+ * a[N], 2 more doubles per k-vector and the 6 of T.  A
  * larger batch runs as consecutive passes.  Applies to every batch form; cf_get_batch_stats counts
  * them all (a VJP call with all cotangents NULL counts its call and conformations, and no pass). */
 CF_EXPORT int cf_set_batch_limit(cf_handle* h, int32_t max_conformations);

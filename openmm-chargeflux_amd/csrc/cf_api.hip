@@ -103,6 +103,12 @@ struct cf_handle {
     cf::BatchPbcVirialWs batch_pbc_virial;
     double* batch_virial_stage = nullptr;
     int64_t batch_virial_stage_confs = 0;
+    // cf_compute_batch_periodic_virial_vjp: the extra workspace beside `batch_pbc` (the second
+    // coefficient array, qdot, g, a, T) and the host form's staging (pos, the cotangent [9], both
+    // gradient rows); both in H->allocs
+    cf::BatchPbcVirialGradWs batch_pbc_virial_grad;
+    double* batch_virial_grad_stage = nullptr;
+    int64_t batch_virial_grad_stage_confs = 0;
 };
 
 namespace {
@@ -2325,6 +2331,106 @@ CF_EXPORT int cf_compute_batch_periodic_vjp_host(cf_handle* H, int32_t nconf, co
                          [&](const double* pos, const double* eb, const double* qb, const double* fb, double* grad) {
                              return cf_compute_batch_periodic_vjp(H, nconf, pos, boxes_host, eb, qb, fb, grad);
                          });
+    });
+}
+
+// ---- parameter gradients of the virial tensors (cf_kernels_batch_pbc_virial_grad.hip) --------------
+// the pass keeps the periodic forward workspace and coefd, qdot, g, a, T together at or below kBatchAutoBytes
+static int batch_pbc_virial_vjp_pass_size(const cf_handle* H, int nconf) {
+    const size_t per =
+        (cf::batch_pbc_doubles_per_conf(H->h) + cf::batch_pbc_virial_grad_doubles_per_conf(H->h)) * sizeof(double);
+    int64_t lim = H->batch_limit > 0 ? H->batch_limit : (int64_t)std::max<size_t>(1, kBatchAutoBytes / per);
+    lim = std::min<int64_t>(lim, cf::kBatchMaxPass);
+    return (int)std::min<int64_t>(lim, nconf);
+}
+
+CF_EXPORT int cf_compute_batch_periodic_virial_vjp(cf_handle* H, int32_t nconf, const double* pos_dev,
+                                                   const double* boxes_host, const double* virial_bar_dev,
+                                                   double* grad_dev, double* lj_grad_dev) {
+    return guarded([&] {
+        batch_periodic_virial_precheck(H, nconf, pos_dev, boxes_host, "cf_compute_batch_periodic_virial_vjp");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        if (!grad_dev && !lj_grad_dev) return;   // nothing asked for: counted, nothing launched
+        if (!virial_bar_dev) {                   // zero cotangent: exact zeros, no pass
+            if (grad_dev)
+                check_hip(hipMemsetAsync(grad_dev, 0, sizeof(double) * np * (size_t)nconf, h.stream), "memset grad");
+            if (lj_grad_dev)
+                check_hip(hipMemsetAsync(lj_grad_dev, 0, sizeof(double) * 2 * n * (size_t)nconf, h.stream),
+                          "memset lj grad");
+            return;
+        }
+        const int pass = batch_pbc_virial_vjp_pass_size(H, nconf);
+        if (pass > H->batch_pbc.cap) {   // first call or growth: allocates (and so synchronises)
+            double* old = H->batch_pbc.base;
+            H->batch_pbc = cf::BatchPbcWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_pbc_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_pbc_carve(h, base, pass, H->batch_pbc);
+        }
+        if (pass > H->batch_pbc_virial_grad.cap) {
+            double* old = H->batch_pbc_virial_grad.base;
+            H->batch_pbc_virial_grad = cf::BatchPbcVirialGradWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_pbc_virial_grad_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_pbc_virial_grad_carve(h, base, pass, H->batch_pbc_virial_grad);
+        }
+        batch_boxes_upload(H, nconf, boxes_host);
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events (as cf_compute_batch_periodic)
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            cf::launch_batch_pbc_virial_vjp(h, H->batch_pbc, H->batch_pbc_virial_grad, m, pos_dev + 3 * n * c0,
+                                            H->batch_boxes_dev + 8 * (size_t)c0, virial_bar_dev + 9 * (size_t)c0,
+                                            grad_dev ? grad_dev + np * c0 : nullptr,
+                                            lj_grad_dev ? lj_grad_dev + 2 * n * c0 : nullptr);
+            H->batch_passes++;
+        }
+        launch_check(h, "compute_batch_periodic_virial_vjp");
+    });
+}
+
+// synchronous host form: positions and the cotangent up through a staging buffer of the handle, the
+// gradient rows back
+CF_EXPORT int cf_compute_batch_periodic_virial_vjp_host(cf_handle* H, int32_t nconf, const double* pos_host,
+                                                        const double* boxes_host, const double* virial_bar_host,
+                                                        double* grad_host, double* lj_grad_host) {
+    return guarded([&] {
+        batch_periodic_virial_precheck(H, nconf, pos_host, boxes_host, "cf_compute_batch_periodic_virial_vjp_host");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, B = (size_t)nconf;
+        const size_t np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+        if (nconf > H->batch_virial_grad_stage_confs) {
+            double* old = H->batch_virial_grad_stage;
+            H->batch_virial_grad_stage = nullptr; H->batch_virial_grad_stage_confs = 0;
+            dfree(H, old);
+            H->batch_virial_grad_stage = dalloc<double>(H, B * (3 * n + 9 + np + 2 * n));
+            H->batch_virial_grad_stage_confs = nconf;
+        }
+        double* pos = H->batch_virial_grad_stage;
+        double* vb = pos + 3 * n * B;
+        double* grad = vb + 9 * B;
+        double* ljg = grad + np * B;
+        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D positions");
+        if (virial_bar_host)
+            check_hip(hipMemcpyAsync(vb, virial_bar_host, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h.stream),
+                      "H2D virial cotangent");
+        const int rc = cf_compute_batch_periodic_virial_vjp(H, nconf, pos, boxes_host, virial_bar_host ? vb : nullptr,
+                                                            grad_host ? grad : nullptr, lj_grad_host ? ljg : nullptr);
+        if (rc != CF_OK) throw CfError(rc, g_err);
+        if (grad_host)
+            check_hip(hipMemcpyAsync(grad_host, grad, sizeof(double) * np * B, hipMemcpyDeviceToHost, h.stream), "D2H grad");
+        if (lj_grad_host)
+            check_hip(hipMemcpyAsync(lj_grad_host, ljg, sizeof(double) * 2 * n * B, hipMemcpyDeviceToHost, h.stream),
+                      "D2H lj grad");
+        check_hip(hipStreamSynchronize(h.stream), "sync");
     });
 }
 

@@ -431,6 +431,29 @@ void launch_batch_pbc_vjp(Handle& h, const BatchPbcWs& w, const BatchPbcGradWs& 
                           const double* boxes, const double* e_bar, const double* q_bar, const double* f_bar,
                           double* grad);
 
+// parameter gradients of the virial tensors (cf_kernels_batch_pbc_virial_grad.hip,
+// cf_compute_batch_periodic_virial_vjp): the extra workspace of one pass beside BatchPbcWs, carved
+// from one allocation of cap * batch_pbc_virial_grad_doubles_per_conf doubles (the double2 array
+// first: 16-B aligned)
+struct BatchPbcVirialGradWs {
+    double* base = nullptr;
+    int cap = 0;                // conformations the arrays hold
+    double2* coefd = nullptr;   // [cap][khalf] 2 c_k Sq + 2 cdot_k S: the coefficient's tangent along the strain
+    double* qdot = nullptr;     // [cap][N] tangent of the charges along the strain
+    double* g = nullptr;        // [cap][N] dE/dq
+    double* a = nullptr;        // [cap][N] -h, h = D_T g (the pair kernel's part of h until k_bpvg_recip)
+    double* t6 = nullptr;       // [cap][6] T = (W_bar + W_bar^T) / 2 as (xx, xy, xz, yy, yz, zz)
+};
+size_t batch_pbc_virial_grad_doubles_per_conf(const Handle& h);
+void batch_pbc_virial_grad_carve(const Handle& h, double* base, int cap, BatchPbcVirialGradWs& w);
+// one pass of nconf <= min(w.cap, vw.cap) conformations on h.stream: at most nine launches, whatever
+// nconf.  boxes: device, [nconf][8] as launch_batch_pbc, every box orthorhombic (the caller has
+// checked); virial_bar [nconf][9]: device, not null; grad [nconf][N + 2 nb + 2 na + 5 nw] and lj_grad
+// [nconf][2 N]: device, overwritten, one of them may be null (grad null: two launches)
+void launch_batch_pbc_virial_vjp(Handle& h, const BatchPbcWs& w, const BatchPbcVirialGradWs& vw, int nconf,
+                                 const double* pos, const double* boxes, const double* virial_bar, double* grad,
+                                 double* lj_grad);
+
 // LJ sigma / epsilon gradients of both batches (cf_kernels_batch_lj_grad.hip, cf_compute_batch_lj_vjp):
 // one pass of nconf <= kBatchMaxPass conformations on h.stream, one launch, no workspace.  boxes:
 // device, [nconf][8] as launch_batch_pbc on a periodic handle, null on a non-periodic one; e_bar

@@ -165,6 +165,9 @@ SIGNATURES = [
     ("cf_compute_batch_periodic_virial", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, DP, C.c_int, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cf_compute_batch_periodic_virial_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, C.c_int, DP, DP, DP, DP]),
+    ("cf_compute_batch_periodic_virial_vjp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, DP, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]),
+    ("cf_compute_batch_periodic_virial_vjp_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP, DP, DP]),
 ]
 
 _lib = None

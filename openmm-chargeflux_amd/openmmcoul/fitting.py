@@ -23,6 +23,13 @@ only -- not for the positions or the boxes.
     loss = ((dipoles - target) ** 2).sum()
     loss.backward()                                   # q.grad, bonds.grad, angles.grad, waters.grad
 
+    energies, forces, charges, virials = model.virials(q, bonds, angles, waters, positions, boxes)
+    loss = ((virials - target) ** 2).sum()            # stress / pressure matching, orthorhombic frames
+    loss.backward()
+
+virials() is cf_compute_batch_periodic_virial forward; backward adds one
+cf_compute_batch_periodic_virial_vjp for the virials' cotangent to the calls above.
+
 dipoles() is cf_compute_batch_dipole forward and one cf_compute_batch_dipole_vjp backward: the dipole
 mu = sum_a q_a x_a about the coordinate origin (that of a charged system moves with a translation) and
 the atomic polar tensors apts[c, b, i, j] = d mu_i / d x_bj, charge-flux part included.
@@ -92,6 +99,69 @@ class _BatchFn(torch.autograd.Function):
             for slot, (t, need) in enumerate(zip(ctx.lj, ctx.needs_input_grad[5:7])):
                 lj[slot] = g[slot * n:(slot + 1) * n].reshape(t.shape).to(t.device) if need else None
         return (None, *out, *lj, None, None)
+
+
+class _VirialFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, charges, bonds, angles, waters, sigmas, epsilons, positions, boxes):
+        given = (charges, bonds, angles, waters) + (() if sigmas is None else (sigmas, epsilons))
+        params = tuple(t.detach().to("cpu", torch.float64).contiguous() for t in given)
+        model._load(params)
+        k = model.kernel
+        nconf, n = positions.shape[0], positions.shape[1]
+        energies = torch.empty(nconf, dtype=torch.float64, device=positions.device)
+        forces = torch.zeros((nconf, n, 3), dtype=torch.float64, device=positions.device)
+        q = torch.empty((nconf, n), dtype=torch.float64, device=positions.device)
+        virials = torch.empty((nconf, 3, 3), dtype=torch.float64, device=positions.device)
+        model._before()
+        k.execute_batch_virial_device(positions, True, True, forces, energies, q, virials, boxes=boxes)
+        model._after()
+        ctx.set_materialize_grads(False)   # an output the loss does not use: a None (NULL) cotangent
+        ctx.model, ctx.params, ctx.loaded = model, params, model._loads
+        ctx.inputs = (charges, bonds, angles, waters)
+        ctx.lj = None if sigmas is None else (sigmas, epsilons)
+        ctx.boxes = boxes.copy()   # the caller may change its array before backward
+        ctx.save_for_backward(positions)
+        return energies, forces, q, virials
+
+    @staticmethod
+    def backward(ctx, e_bar, f_bar, q_bar, v_bar):
+        # the energy, force and charge cotangents: the periodic VJP and LJ VJP calls of __call__,
+        # skipped when the loss uses none of the three
+        out = [None] * 9 if e_bar is None and f_bar is None and q_bar is None \
+            else list(_BatchFn.backward(ctx, e_bar, f_bar, q_bar))
+        if v_bar is None:
+            return tuple(out)
+        model = ctx.model
+        k = model.kernel
+        (positions,) = ctx.saved_tensors
+        if model._loads != ctx.loaded:   # another forward has changed the parameters since: put these back
+            model._load(ctx.params)
+            ctx.loaded = model._loads
+        nconf, n = positions.shape[0], positions.shape[1]
+        need, need_lj = ctx.needs_input_grad[1:5], ctx.lj is not None and any(ctx.needs_input_grad[5:7])
+        counts = k.param_counts()
+        grad = torch.empty((nconf, sum(counts)), dtype=torch.float64, device=positions.device) if any(need) else None
+        lj_grad = torch.empty((nconf, 2 * n), dtype=torch.float64, device=positions.device) if need_lj else None
+        if grad is None and lj_grad is None:
+            return tuple(out)
+        # queued on torch's stream before _before() orders it ahead of the kernel's; alive until _after()
+        cot = v_bar.detach().to(torch.float64).contiguous()
+        model._before()
+        k.execute_batch_virial_vjp_device(positions, ctx.boxes, grad, cot, lj_grad)
+        model._after()
+        add = lambda old, g, t: g.reshape(t.shape).to(t.device) if old is None else old + g.reshape(t.shape).to(t.device)
+        if grad is not None:
+            g = k.split_gradient(grad.sum(dim=0, keepdim=True), counts)
+            for slot, (t, name) in enumerate(zip(ctx.inputs, ("charges", "bonds", "angles", "waters"))):
+                if need[slot]:
+                    out[1 + slot] = add(out[1 + slot], g[name][0], t)
+        if lj_grad is not None:
+            g = lj_grad.sum(dim=0)
+            for slot, t in enumerate(ctx.lj):
+                if ctx.needs_input_grad[5 + slot]:
+                    out[5 + slot] = add(out[5 + slot], g[slot * n:(slot + 1) * n], t)
+        return tuple(out)
 
 
 class _DipoleFn(torch.autograd.Function):
@@ -211,6 +281,27 @@ class BatchedChargeFlux:
         if boxes is not None:   # before the parameters are loaded
             self.kernel._batch_boxes(boxes, positions.shape[0])
         return _BatchFn.apply(self, charges, bonds, angles, waters, sigmas, epsilons, positions, boxes)
+
+    def virials(self, charges, bonds, angles, waters, positions, boxes, *, sigmas=None, epsilons=None):
+        """(energies (B,), forces (B,N,3), charges (B,N), virials (B,3,3)) of B periodic frames in
+        orthorhombic boxes as a differentiable function of the parameters (arguments as __call__,
+        boxes required).  The first three are bitwise what __call__ returns; virials[c] = -dE/d(strain)
+        is what execute_batch_virial_device writes (cf_compute_batch_periodic_virial).  Backward makes
+        the calls of __call__ for the energy, force and charge cotangents and adds one
+        cf_compute_batch_periodic_virial_vjp for the virials' cotangent (flux parameters and, with
+        sigmas= and epsilons=, the LJ parameters in the same call); a loss that does not use the
+        virials skips that call, and one that uses the virials alone skips the others."""
+        if (sigmas is None) != (epsilons is None):
+            raise ValueError("sigmas and epsilons must be given together, or neither")
+        lj = () if sigmas is None else ((sigmas, "sigmas"), (epsilons, "epsilons"))
+        for t, name in ((charges, "charges"), (bonds, "bonds"), (angles, "angles"), (waters, "waters"),
+                        (positions, "positions")) + lj:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise ValueError(f"{name} must be a float64 torch tensor")
+        if positions.requires_grad:
+            raise ValueError("positions must not require grad: gradients with respect to positions are not computed")
+        boxes = self.kernel._batch_boxes(boxes, positions.shape[0])   # before the parameters are loaded
+        return _VirialFn.apply(self, charges, bonds, angles, waters, sigmas, epsilons, positions, boxes)
 
     def dipoles(self, charges, bonds, angles, waters, positions):
         """Dipoles (B,3) and atomic polar tensors (B,N,3,3) of B conformations of a non-periodic

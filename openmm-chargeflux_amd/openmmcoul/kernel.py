@@ -392,6 +392,54 @@ class HipCalcCoulForceKernel:
             self._flags(includeForces, includeEnergy), ptr(forces), ptr(energies), ptr(charges), ptr(virials)),
             self._lib)
 
+    # parameter gradients of the virial tensors (cf_compute_batch_periodic_virial_vjp) ------------------
+    def execute_batch_virial_vjp_host(self, positions, boxes, virial_bar=None, lj=False):
+        """Gradients of L = virial_bar : virial (the tensors of execute_batch_virial_host) with respect
+        to the base charges and the flux parameters, per frame
+        (cf_compute_batch_periodic_virial_vjp_host).  positions (B,N,3), virial_bar (B,3,3):
+        C-contiguous float64 numpy arrays, boxes as execute_batch_host (orthorhombic); virial_bar None
+        = zero.  Returns the dict of execute_batch_vjp_host (split_gradient); lj=True adds sigmas (B,N)
+        and epsilons (B,N), the gradients with respect to every atom's LJ parameters (exactly 0 for an
+        atom with epsilon = 0), views of one (B,2N) array returned as lj_flat."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        b = self._batch_boxes(boxes, nconf)
+        if virial_bar is not None and (not isinstance(virial_bar, np.ndarray)
+                                       or self._check_batch_array(virial_bar, "virial_bar", (3, 3)) != nconf):
+            raise ValueError(f"virial_bar must be a float64 ndarray for {nconf} conformations")
+        counts = self.param_counts()
+        flat = np.zeros((nconf, sum(counts)))
+        lj_flat = np.zeros((nconf, 2 * self._n)) if lj else None
+        opt = lambda a: _dp(a) if a is not None else None
+        _cabi.check(self._lib.cf_compute_batch_periodic_virial_vjp_host(
+            self._h, nconf, _dp(positions), _dp(b), opt(virial_bar), _dp(flat), opt(lj_flat)), self._lib)
+        out = self.split_gradient(flat, counts)
+        if lj:
+            out.update(lj_flat=lj_flat, sigmas=lj_flat[:, :self._n], epsilons=lj_flat[:, self._n:])
+        return out
+
+    def execute_batch_virial_vjp_device(self, positions, boxes, grad=None, virial_bar=None, lj_grad=None):
+        """The same on torch tensors (float64, on the kernel's device, contiguous): grad (B,P) and
+        lj_grad (B,2N), sigmas then epsilons per frame, are overwritten; either may be None.
+        Asynchronous on the kernel's stream; boxes a numpy array in HOST memory, read during the call."""
+        import torch
+        if not isinstance(positions, torch.Tensor):
+            raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
+        b = self._batch_boxes(boxes, nconf)
+        # grad: (B, anything), dtype and contiguity first; its width against P needs the handle
+        for t, name, trailing in ((virial_bar, "virial_bar", (3, 3)), (lj_grad, "lj_grad", (2 * self._n,)),
+                                  (grad, "grad", (grad.shape[1],) if isinstance(grad, torch.Tensor) and grad.dim() == 2 else (-1,))):
+            if t is not None and (not isinstance(t, torch.Tensor)
+                                  or self._check_batch_array(t, name, trailing, torch) != nconf):
+                raise ValueError(f"{name} must be a float64 torch tensor for {nconf} conformations")
+        if grad is not None and grad.shape[1] != sum(self.param_counts()):
+            raise ValueError(f"grad must have shape (B, P) with P = {sum(self.param_counts())}")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _cabi.check(self._lib.cf_compute_batch_periodic_virial_vjp(
+            self._h, nconf, ptr(positions), _dp(b), ptr(virial_bar), ptr(grad), ptr(lj_grad)), self._lib)
+
     # parameter gradients of the batch (cf_compute_batch_vjp; boxes=: cf_compute_batch_periodic_vjp) --
     def param_counts(self):
         """(N, 2 * bonds, 2 * angles, 5 * waters): the lengths of the four parameter groups of a
