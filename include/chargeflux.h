@@ -40,7 +40,8 @@ extern "C" {
                               cf_compute_batch_hvp_host; cf_compute_batch_periodic_hvp,
                               cf_compute_batch_periodic_hvp_host; cf_compute_batch_periodic_virial,
                               cf_compute_batch_periodic_virial_host; cf_compute_batch_periodic_virial_vjp,
-                              cf_compute_batch_periodic_virial_vjp_host */
+                              cf_compute_batch_periodic_virial_vjp_host; cf_compute_batch_esp,
+                              cf_compute_batch_esp_host, cf_compute_batch_esp_vjp, cf_compute_batch_esp_vjp_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -578,6 +579,70 @@ CF_EXPORT int cf_compute_batch_dipole_vjp_host(cf_handle* h, int32_t nconf, cons
                                                const double* dipole_bar_host, const double* apt_bar_host,
                                                double* grad_host);
 /*
+ * Electrostatic potential (ESP) of the non-periodic batch at probe points -- what a RESP-style fit to
+ * a QM potential on vdW shells targets.  Per conformation, with q the charges after flux (exactly
+ * cf_compute_batch's charges, to the bit) and ke the handle's one_4pi_eps0:
+ *   V[p] = ke sum_a q_a / |r_p - x_a|                                  (kJ/mol/e)
+ * over EVERY atom: exclusions play no part, LJ plays no part.
+ *   pos_dev      [nconf][N][3] fp64 DEVICE, nm, conformation-major
+ *   npts         probe points per conformation, the same for all of them (a caller with ragged grids
+ *                pads with a repeated real point and a zero cotangent)
+ *   points_dev   [nconf][npts][3] fp64 DEVICE, nm
+ *   esp_dev      [nconf][npts] fp64 DEVICE, or NULL
+ *   charges_dev  [nconf][N] fp64 DEVICE, or NULL
+ * Both outputs are OVERWRITTEN.  A point that coincides with an atom is the caller's error: it gives
+ * a non-finite value and is NOT checked.  With both outputs NULL the call and its conformations are
+ * counted and nothing is launched.  A pass is at most three kernel launches whatever nconf and npts
+ * (flux terms, charges, one kernel for V), in the batch workspace of cf_compute_batch with its pass
+ * size.
+ *
+ * cf_compute_batch_esp_vjp: the reverse-mode product with respect to the base charges and the flux
+ * parameters.  Per conformation, with the cotangent V_bar[npts], the scalar is L = sum_p V_bar_p V_p.
+ *   esp_bar_dev  [nconf][npts] fp64 DEVICE, or NULL (= zero)
+ *   grad_dev     [nconf][P] fp64 DEVICE, OVERWRITTEN: rows in the order of cf_get_param_counts, as
+ *                cf_compute_batch_vjp; not summed over the conformations
+ * With esp_bar_dev NULL grad is set to exact zeros (one memset; the call and its conformations are
+ * counted, no pass).  Closed form: with a_i = ke sum_p V_bar_p / |r_p - x_i|, the gradient is that of
+ * sum_i a_i q_i with a fixed.  Every flux term is a sum of pieces q_a += c_a k (g(x) - ref) over its
+ * atoms (the pieces of cf_compute_batch_dipole_vjp):
+ *   dL/d(base charge i) = a_i
+ *   dL/dk   += (sum_a c_a a_a) (g - ref)
+ *   dL/dref += -k sum_a c_a a_a
+ * Nothing divides by a parameter: a term with k = 0 is legal.  At most three kernel launches per pass
+ * (the adjoint weights a, an ordered sum when npts spans several chunks of CF_BATCH_ESP_CHUNK points,
+ * the terms); a scratch array [pass][chunks][N] is allocated on first need (growth synchronises) and
+ * freed by cf_destroy.  A pass is min(cf_set_batch_limit or automatic, nconf) conformations.
+ *
+ * Guarantee: no atomics, and every sum's order depends only on N, npts and the topology (a point's
+ * sum runs over the atoms in index order; an atom's over the points in a fixed order).  A
+ * conformation's potentials and gradient row are bitwise the same alone, at any position of any
+ * batch, under any pass size and in the host and the device form, and a point's potential does not
+ * depend on the other points of the call.
+ *
+ * Errors and states of both: a periodic handle CF_ERR_INVALID ("non-periodic": a periodic potential
+ * needs an Ewald sum of its own); world_size > 1 or a call between cf_compute_begin and _end
+ * CF_ERR_STATE; NULL pos, NULL points, NULL grad, nconf < 0 or npts < 0 CF_ERR_INVALID; nconf = 0 or
+ * npts = 0 is a no-op that counts nothing and writes nothing (charges_dev included); a NULL handle is
+ * rejected without touching a device; a guard bit already set fails the call.  Always fp64, eager
+ * launches on the handle's stream (never captured or replayed, not recorded by cf_set_timing),
+ * asynchronous: inputs and outputs must stay valid until the stream reaches them.
+ * cf_get_batch_stats counts both; cf_compute's state and diagnostics are not touched; both read the
+ * parameter buffers cf_update_parameters last wrote.  No guard bits.  Out of scope: periodic handles,
+ * the field at the points, ragged point counts, gradients with respect to positions or points.
+ */
+#define CF_BATCH_ESP_CHUNK 4096   /* points per chunk of the VJP's sum over the points (build-time) */
+CF_EXPORT int cf_compute_batch_esp(cf_handle* h, int32_t nconf, const double* pos_dev, int32_t npts,
+                                   const double* points_dev, double* esp_dev, double* charges_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_esp_host(cf_handle* h, int32_t nconf, const double* pos_host, int32_t npts,
+                                        const double* points_host, double* esp_host, double* charges_host);
+CF_EXPORT int cf_compute_batch_esp_vjp(cf_handle* h, int32_t nconf, const double* pos_dev, int32_t npts,
+                                       const double* points_dev, const double* esp_bar_dev, double* grad_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_esp_vjp_host(cf_handle* h, int32_t nconf, const double* pos_host, int32_t npts,
+                                            const double* points_host, const double* esp_bar_host,
+                                            double* grad_host);
+/*
  * Hessian-vector products of the non-periodic batch -- normal modes (with the polar tensors: IR
  * spectra), Newton-CG geometry optimisation, harmonic validation of a fitted model.  H = d2E/dxdx is
  * the Hessian with respect to the positions of exactly the energy cf_compute_batch returns with both
@@ -775,7 +840,9 @@ CF_EXPORT int cf_compute_batch_periodic_virial_vjp_host(cf_handle* h, int32_t nc
  * periodic batch also the phase tables, 4 doubles per [N][kmax_x + kmax_y + kmax_z] entry, and 3
  * doubles per k-vector; cf_compute_batch_vjp also qdot[N], g[N], a[N]; cf_compute_batch_periodic_vjp
  * those three and 2 more doubles per k-vector) at or below 256 MiB, and never more than 65535
- * (cf_compute_batch_lj_vjp and cf_compute_batch_dipole_vjp have no workspace: automatic is 65535).
+ * (cf_compute_batch_lj_vjp and cf_compute_batch_dipole_vjp have no workspace: automatic is 65535;
+ * neither has cf_compute_batch_esp_vjp up to CF_BATCH_ESP_CHUNK points, beyond that its scratch is
+ * ceil(npts / CF_BATCH_ESP_CHUNK) * N doubles per conformation).
  * cf_compute_batch_hvp: a pass is conformations x directions with conformations * directions <= 65535;
  * per conformation the doubles of cf_compute_batch, per (conformation, direction) S + 3 D + 3 N more
  * (S charge slots: 2 per bond, 3 per angle or water; D dq/dx entries: 4 per bond, 9 per angle or

@@ -90,6 +90,11 @@ struct cf_handle {
     // batch_dipole_stage (in H->allocs)
     double* batch_dipole_stage = nullptr;
     int64_t batch_dipole_stage_confs = 0;
+    // cf_compute_batch_esp uses `batch`; its VJP the partial sums of batch_esp when the points span
+    // several chunks; both host forms stage through batch_esp_stage (all in H->allocs)
+    cf::BatchEspWs batch_esp;
+    double* batch_esp_stage = nullptr;
+    size_t batch_esp_stage_doubles = 0;
     // cf_compute_batch_hvp: the extra workspace beside `batch`, a row per (conformation, direction)
     // of a pass, and the host form's staging buffer: pos, directions, products (both in H->allocs)
     cf::BatchHvpWs batch_hvp;
@@ -2666,6 +2671,172 @@ CF_EXPORT int cf_compute_batch_dipole_vjp_host(cf_handle* H, int32_t nconf, cons
                       "H2D polar tensor cotangent");
         const int rc = cf_compute_batch_dipole_vjp(H, nconf, pos, dipole_bar_host ? mb : nullptr,
                                                    apt_bar_host ? pb : nullptr, grad);
+        if (rc != CF_OK) throw CfError(rc, g_err);
+        check_hip(hipMemcpyAsync(grad_host, grad, sizeof(double) * np * B, hipMemcpyDeviceToHost, h.stream), "D2H grad");
+        check_hip(hipStreamSynchronize(h.stream), "sync");
+    });
+}
+
+// ---- electrostatic potential at probe points of the non-periodic batch (cf_kernels_batch_esp.hip) ---
+// Everything that can refuse either call, before anything is launched, staged or counted; grad: the
+// VJP's output (required there)
+static void batch_esp_precheck(cf_handle* H, int32_t nconf, const double* pos, int32_t npts, const double* points,
+                               bool need_grad, const double* grad, const char* name) {
+    if (!H || !pos || !points || (need_grad && !grad)) fail(CF_ERR_INVALID, "null argument");
+    if (nconf < 0) fail(CF_ERR_INVALID, "nconf must be >= 0");
+    if (npts < 0) fail(CF_ERR_INVALID, "npts must be >= 0");
+    cf::Handle& h = H->h;
+    if (h.world > 1) fail(CF_ERR_STATE, std::string(name) + " is single-rank only");
+    if (h.pbc) fail(CF_ERR_INVALID, std::string(name) + ": batches are non-periodic only (this handle is periodic)");
+    if (h.pending_flags >= 0) fail(CF_ERR_STATE, std::string(name) + " during a begun evaluation");
+    guard_check(h);
+}
+
+// the staging buffer of both host forms: positions, points, a row of npts doubles (the potentials or
+// their cotangent) and a row of P >= N doubles (the charges or the gradient) per conformation
+static double* batch_esp_stage(cf_handle* H, size_t need) {
+    if (need > H->batch_esp_stage_doubles) {
+        double* old = H->batch_esp_stage;
+        H->batch_esp_stage = nullptr; H->batch_esp_stage_doubles = 0;
+        dfree(H, old);
+        H->batch_esp_stage = dalloc<double>(H, need);
+        H->batch_esp_stage_doubles = need;
+    }
+    return H->batch_esp_stage;
+}
+
+CF_EXPORT int cf_compute_batch_esp(cf_handle* H, int32_t nconf, const double* pos_dev, int32_t npts,
+                                   const double* points_dev, double* esp_dev, double* charges_dev) {
+    return guarded([&] {
+        batch_esp_precheck(H, nconf, pos_dev, npts, points_dev, false, nullptr, "cf_compute_batch_esp");
+        if (nconf == 0 || npts == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        if (!esp_dev && !charges_dev) return;   // nothing asked for: counted, nothing launched
+        const int pass = batch_pass_size(H, nconf);
+        if (pass > H->batch.cap) {   // first call or growth: allocates (and so synchronises)
+            double* old = H->batch.base;
+            H->batch = cf::BatchWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_carve(h, base, pass, H->batch);
+        }
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events (as cf_compute_batch)
+        const size_t n = (size_t)h.n, M = (size_t)npts;
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            cf::launch_batch_esp(h, H->batch, m, pos_dev + 3 * n * c0, npts, points_dev + 3 * M * c0,
+                                 esp_dev ? esp_dev + M * c0 : nullptr, charges_dev ? charges_dev + n * c0 : nullptr);
+            H->batch_passes++;
+        }
+        launch_check(h, "compute_batch_esp");
+    });
+}
+
+// synchronous host form: positions and points up through a staging buffer of the handle, the outputs back
+CF_EXPORT int cf_compute_batch_esp_host(cf_handle* H, int32_t nconf, const double* pos_host, int32_t npts,
+                                        const double* points_host, double* esp_host, double* charges_host) {
+    return guarded([&] {
+        batch_esp_precheck(H, nconf, pos_host, npts, points_host, false, nullptr, "cf_compute_batch_esp_host");
+        if (nconf == 0 || npts == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, B = (size_t)nconf, M = (size_t)npts;
+        double* pos = batch_esp_stage(H, B * (3 * n + 3 * M + M + n));
+        double* pts = pos + 3 * n * B;
+        double* esp = pts + 3 * M * B;
+        double* chg = esp + M * B;
+        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D positions");
+        check_hip(hipMemcpyAsync(pts, points_host, sizeof(double) * 3 * M * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D points");
+        const int rc = cf_compute_batch_esp(H, nconf, pos, npts, pts, esp_host ? esp : nullptr,
+                                            charges_host ? chg : nullptr);
+        if (rc != CF_OK) throw CfError(rc, g_err);
+        if (esp_host)
+            check_hip(hipMemcpyAsync(esp_host, esp, sizeof(double) * M * B, hipMemcpyDeviceToHost, h.stream),
+                      "D2H potentials");
+        if (charges_host)
+            check_hip(hipMemcpyAsync(charges_host, chg, sizeof(double) * n * B, hipMemcpyDeviceToHost, h.stream),
+                      "D2H charges");
+        check_hip(hipStreamSynchronize(h.stream), "sync");
+    });
+}
+
+// one chunk of points: no workspace, the pass of cf_compute_batch_lj_vjp; several: the partial sums
+// [pass][chunks][N] stay at or below kBatchAutoBytes
+static int batch_esp_vjp_pass_size(const cf_handle* H, int nconf, int chunks) {
+    if (chunks == 1) return batch_lj_pass_size(H, nconf);
+    const size_t per = (size_t)chunks * (size_t)H->h.n * sizeof(double);
+    int64_t lim = H->batch_limit > 0 ? H->batch_limit : (int64_t)std::max<size_t>(1, kBatchAutoBytes / per);
+    lim = std::min<int64_t>(lim, cf::kBatchMaxPass);
+    return (int)std::min<int64_t>(lim, nconf);
+}
+
+CF_EXPORT int cf_compute_batch_esp_vjp(cf_handle* H, int32_t nconf, const double* pos_dev, int32_t npts,
+                                       const double* points_dev, const double* esp_bar_dev, double* grad_dev) {
+    return guarded([&] {
+        batch_esp_precheck(H, nconf, pos_dev, npts, points_dev, true, grad_dev, "cf_compute_batch_esp_vjp");
+        if (nconf == 0 || npts == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+        const size_t M = (size_t)npts;
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        if (!esp_bar_dev) {   // zero cotangent: exact zeros, no pass
+            check_hip(hipMemsetAsync(grad_dev, 0, sizeof(double) * np * (size_t)nconf, h.stream), "memset grad");
+            return;
+        }
+        const int chunks = cf::batch_esp_chunks(npts);
+        const int pass = batch_esp_vjp_pass_size(H, nconf, chunks);
+        const size_t need = chunks > 1 ? (size_t)pass * (size_t)chunks * n : 0;
+        if (need > H->batch_esp.doubles) {   // first need or growth: allocates (and so synchronises)
+            double* old = H->batch_esp.part;
+            H->batch_esp = cf::BatchEspWs();
+            dfree(H, old);
+            H->batch_esp.part = dalloc<double>(H, need);
+            H->batch_esp.doubles = need;
+        }
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events (as cf_compute_batch)
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            cf::launch_batch_esp_vjp(h, m, pos_dev + 3 * n * c0, npts, points_dev + 3 * M * c0, esp_bar_dev + M * c0,
+                                     chunks > 1 ? H->batch_esp.part : nullptr, grad_dev + np * c0);
+            H->batch_passes++;
+        }
+        launch_check(h, "compute_batch_esp_vjp");
+    });
+}
+
+// synchronous host form: positions, points and the cotangent up through the same staging buffer, the
+// gradients back
+CF_EXPORT int cf_compute_batch_esp_vjp_host(cf_handle* H, int32_t nconf, const double* pos_host, int32_t npts,
+                                            const double* points_host, const double* esp_bar_host,
+                                            double* grad_host) {
+    return guarded([&] {
+        batch_esp_precheck(H, nconf, pos_host, npts, points_host, true, grad_host, "cf_compute_batch_esp_vjp_host");
+        if (nconf == 0 || npts == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, B = (size_t)nconf, M = (size_t)npts;
+        const size_t np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+        double* pos = batch_esp_stage(H, B * (3 * n + 3 * M + M + np));
+        double* pts = pos + 3 * n * B;
+        double* vb = pts + 3 * M * B;
+        double* grad = vb + M * B;
+        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D positions");
+        check_hip(hipMemcpyAsync(pts, points_host, sizeof(double) * 3 * M * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D points");
+        if (esp_bar_host)
+            check_hip(hipMemcpyAsync(vb, esp_bar_host, sizeof(double) * M * B, hipMemcpyHostToDevice, h.stream),
+                      "H2D potential cotangent");
+        const int rc = cf_compute_batch_esp_vjp(H, nconf, pos, npts, pts, esp_bar_host ? vb : nullptr, grad);
         if (rc != CF_OK) throw CfError(rc, g_err);
         check_hip(hipMemcpyAsync(grad_host, grad, sizeof(double) * np * B, hipMemcpyDeviceToHost, h.stream), "D2H grad");
         check_hip(hipStreamSynchronize(h.stream), "sync");

@@ -473,6 +473,25 @@ void launch_batch_dipole(Handle& h, const BatchWs& w, int nconf, const double* p
 void launch_batch_dipole_vjp(Handle& h, int nconf, const double* pos, const double* dipole_bar, const double* apt_bar,
                              double* grad);
 
+// electrostatic potential at probe points of the non-periodic batch (cf_kernels_batch_esp.hip,
+// cf_compute_batch_esp): one pass of nconf <= w.cap conformations on h.stream, at most three launches
+// (k_b_flux and k_b_charges into w, then k_be_esp).  points [nconf][npts][3], npts > 0; esp
+// [nconf][npts], charges [nconf][N]: device, overwritten, each may be null
+void launch_batch_esp(Handle& h, const BatchWs& w, int nconf, const double* pos, int npts, const double* points,
+                      double* esp, double* charges);
+// its parameter gradients (cf_compute_batch_esp_vjp): the scratch of one pass, the adjoint weights'
+// partial sums per point chunk, needed only when the points span several chunks
+struct BatchEspWs {
+    double* part = nullptr;     // [cap][chunks][N], chunks = batch_esp_chunks(npts)
+    size_t doubles = 0;         // the allocation's size
+};
+int batch_esp_chunks(int npts);   // point chunks of the adjoint kernel: ceil(npts / CF_BATCH_ESP_CHUNK)
+// one pass of nconf <= kBatchMaxPass conformations on h.stream, at most three launches.  esp_bar
+// [nconf][npts]: device, not null; part: null when batch_esp_chunks(npts) = 1, else nconf * chunks * N
+// doubles; grad [nconf][N + 2 nb + 2 na + 5 nw] overwritten
+void launch_batch_esp_vjp(Handle& h, int nconf, const double* pos, int npts, const double* points,
+                          const double* esp_bar, double* part, double* grad);
+
 // Hessian-vector products of the non-periodic batch (cf_kernels_batch_hvp.hip, cf_compute_batch_hvp):
 // the extra workspace of one pass beside BatchWs, one row per (conformation, direction) of the pass,
 // carved from one allocation of cap * batch_hvp_doubles_per_row doubles

@@ -51,6 +51,7 @@ CF_ENERGY_DOUBLE = 0
 CF_ENERGY_FLOAT = 1
 CF_INCLUDE_FORCES = 1
 CF_INCLUDE_ENERGY = 2
+CF_BATCH_ESP_CHUNK = 4096   # points per chunk of cf_compute_batch_esp_vjp's sum over the points
 ONE_4PI_EPS0 = 138.935456                    # OpenMM 7.x headers: cf_params.one_4pi_eps0 = 0
 ONE_4PI_EPS0_CODATA2018 = 138.93545764438198  # OpenMM 8.x headers (CODATA 2018)
 
@@ -157,6 +158,11 @@ SIGNATURES = [
     ("cf_compute_batch_dipole_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP, DP]),
     ("cf_compute_batch_dipole_vjp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cf_compute_batch_dipole_vjp_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP, DP]),
+    ("cf_compute_batch_esp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cf_compute_batch_esp_host", C.c_int, [C.c_void_p, C.c_int32, DP, C.c_int32, DP, DP, DP]),
+    ("cf_compute_batch_esp_vjp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    ("cf_compute_batch_esp_vjp_host", C.c_int, [C.c_void_p, C.c_int32, DP, C.c_int32, DP, DP, DP]),
     ("cf_compute_batch_hvp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     ("cf_compute_batch_hvp_host", C.c_int, [C.c_void_p, C.c_int32, DP, C.c_int32, DP, DP]),
     ("cf_compute_batch_periodic_hvp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, DP, C.c_int32, C.c_void_p,

@@ -34,6 +34,13 @@ dipoles() is cf_compute_batch_dipole forward and one cf_compute_batch_dipole_vjp
 mu = sum_a q_a x_a about the coordinate origin (that of a charged system moves with a translation) and
 the atomic polar tensors apts[c, b, i, j] = d mu_i / d x_bj, charge-flux part included.
 
+    potentials = model.esp(q, bonds, angles, waters, positions, points)   # non-periodic: (B,M)
+    loss = ((potentials - target) ** 2).sum()         # RESP-style fit to a QM potential
+    loss.backward()
+
+esp() is cf_compute_batch_esp forward and one cf_compute_batch_esp_vjp backward: the potential
+V_p = ke sum_a q_a / |r_p - x_a| of the charges after flux at M probe points per conformation.
+
 Convention (cf_compute_batch_lj_vjp): an atom with epsilon = 0 receives exactly 0 for its sigma and
 epsilon gradients.  The true derivative of sqrt(eps_i eps_j) is singular there; such an atom has no
 LJ interaction, and an optimiser leaves it at 0.
@@ -204,6 +211,43 @@ class _DipoleFn(torch.autograd.Function):
         return (None, *out, None)
 
 
+class _EspFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, charges, bonds, angles, waters, positions, points):
+        params = tuple(t.detach().to("cpu", torch.float64).contiguous() for t in (charges, bonds, angles, waters))
+        model._load(params)
+        k = model.kernel
+        potentials = torch.empty(points.shape[:2], dtype=torch.float64, device=positions.device)
+        model._before()
+        k.execute_batch_esp_device(positions, points, potentials)
+        model._after()
+        ctx.model, ctx.params, ctx.loaded = model, params, model._loads
+        ctx.inputs = (charges, bonds, angles, waters)
+        ctx.save_for_backward(positions, points)
+        return potentials
+
+    @staticmethod
+    def backward(ctx, esp_bar):
+        model = ctx.model
+        k = model.kernel
+        positions, points = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[1:5]):
+            return (None,) * 7
+        if model._loads != ctx.loaded:   # another forward has changed the parameters since: put these back
+            model._load(ctx.params)
+            ctx.loaded = model._loads
+        cot = esp_bar.detach().to(torch.float64).contiguous()
+        counts = k.param_counts()
+        grad = torch.empty((positions.shape[0], sum(counts)), dtype=torch.float64, device=positions.device)
+        model._before()
+        k.execute_batch_esp_vjp_device(positions, points, grad, cot)
+        model._after()
+        g = k.split_gradient(grad.sum(dim=0, keepdim=True), counts)
+        out = [g[name][0].reshape(t.shape).to(t.device) if need else None
+               for t, name, need in zip(ctx.inputs, ("charges", "bonds", "angles", "waters"), ctx.needs_input_grad[1:5])]
+        return (None, *out, None, None)
+
+
 class BatchedChargeFlux:
     """Energies, forces and charges of B conformations as a differentiable function of the
     parameters.  kernel: a HipCalcCoulForceKernel initialised with `force` (one rank);
@@ -317,3 +361,20 @@ class BatchedChargeFlux:
         if positions.requires_grad:
             raise ValueError("positions must not require grad: gradients with respect to positions are not computed")
         return _DipoleFn.apply(self, charges, bonds, angles, waters, positions)
+
+    def esp(self, charges, bonds, angles, waters, positions, points):
+        """Electrostatic potentials (B,M) in kJ/mol/e of B conformations of a non-periodic system at
+        the probe points points (B,M,3) (nm, float64, contiguous on the kernel's device) as a
+        differentiable function of the four parameter tensors (arguments as __call__;
+        cf_compute_batch_esp forward, one cf_compute_batch_esp_vjp summed over the conformations in
+        backward).  Every atom contributes to every point; a point on an atom gives a non-finite
+        value.  Neither positions nor points may require grad."""
+        for t, name in ((charges, "charges"), (bonds, "bonds"), (angles, "angles"), (waters, "waters"),
+                        (positions, "positions"), (points, "points")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise ValueError(f"{name} must be a float64 torch tensor")
+        if positions.requires_grad or points.requires_grad:
+            raise ValueError("positions and points must not require grad: gradients with respect to them are not computed")
+        if points.dim() != 3 or points.shape[0] != positions.shape[0] or points.shape[2] != 3:   # before the parameters are loaded
+            raise ValueError(f"points must have shape (B, M, 3), got {tuple(points.shape)}")
+        return _EspFn.apply(self, charges, bonds, angles, waters, positions, points)

@@ -623,6 +623,87 @@ class HipCalcCoulForceKernel:
         _cabi.check(self._lib.cf_compute_batch_dipole_vjp(self._h, nconf, ptr(positions), ptr(dipole_bar),
                                                           ptr(apt_bar), ptr(grad)), self._lib)
 
+    # electrostatic potential at probe points of the non-periodic batch (cf_compute_batch_esp, _vjp) ----
+    def _check_esp_points(self, points, nconf, module, kind):
+        if not isinstance(points, kind):
+            raise ValueError(f"points must be a float64 {kind.__name__} of shape (B, M, 3)")
+        shape = tuple(points.shape)
+        if len(shape) != 3:
+            raise ValueError(f"points must have shape (B, M, 3), got {shape}")
+        if self._check_batch_array(points, "points", (shape[1], 3), module) != nconf:
+            raise ValueError(f"points holds {shape[0]} conformations, positions {nconf}")
+        return shape[1]
+
+    def execute_batch_esp_host(self, positions, points):
+        """Electrostatic potential of B conformations at M probe points each
+        (cf_compute_batch_esp_host; non-periodic systems).  positions (B,N,3), points (B,M,3) in nm:
+        C-contiguous float64 numpy arrays.  Returns (potentials (B,M) in kJ/mol/e, V_p = ke sum_a q_a /
+        |r_p - x_a| over every atom, charges (B,N) after flux: execute_batch_host's, to the bit).  A
+        point on an atom gives a non-finite value (not checked)."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        npts = self._check_esp_points(points, nconf, np, np.ndarray)
+        potentials, charges = np.zeros((nconf, npts)), np.zeros((nconf, self._n))
+        _cabi.check(self._lib.cf_compute_batch_esp_host(self._h, nconf, _dp(positions), npts, _dp(points),
+                                                        _dp(potentials), _dp(charges)), self._lib)
+        return potentials, charges
+
+    def execute_batch_esp_device(self, positions, points, potentials=None, charges=None):
+        """The same on torch tensors (float64, on the kernel's device, contiguous): positions
+        (B,N,3), points (B,M,3); potentials (B,M) and charges (B,N) overwritten, each may be None.
+        Asynchronous on the kernel's stream."""
+        import torch
+        if not isinstance(positions, torch.Tensor):
+            raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
+        npts = self._check_esp_points(points, nconf, torch, torch.Tensor)
+        for t, name, trailing in ((potentials, "potentials", (npts,)), (charges, "charges", (self._n,))):
+            if t is not None and (not isinstance(t, torch.Tensor)
+                                  or self._check_batch_array(t, name, trailing, torch) != nconf):
+                raise ValueError(f"{name} must be a float64 torch tensor for {nconf} conformations")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _cabi.check(self._lib.cf_compute_batch_esp(self._h, nconf, ptr(positions), npts, ptr(points), ptr(potentials),
+                                                   ptr(charges)), self._lib)
+
+    def execute_batch_esp_vjp_host(self, positions, points, esp_bar=None):
+        """Gradients of L = sum_p esp_bar_p V_p with respect to the base charges and the flux
+        parameters, per conformation (cf_compute_batch_esp_vjp_host).  positions (B,N,3), points
+        (B,M,3), esp_bar (B,M): C-contiguous float64 numpy arrays; esp_bar may be None (= zero).
+        Returns the dict of execute_batch_vjp_host (split_gradient)."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        npts = self._check_esp_points(points, nconf, np, np.ndarray)
+        if esp_bar is not None and (not isinstance(esp_bar, np.ndarray)
+                                    or self._check_batch_array(esp_bar, "esp_bar", (npts,)) != nconf):
+            raise ValueError(f"esp_bar must be a float64 ndarray for {nconf} conformations")
+        counts = self.param_counts()
+        flat = np.zeros((nconf, sum(counts)))
+        _cabi.check(self._lib.cf_compute_batch_esp_vjp_host(self._h, nconf, _dp(positions), npts, _dp(points),
+                                                            _dp(esp_bar) if esp_bar is not None else None,
+                                                            _dp(flat)), self._lib)
+        return self.split_gradient(flat, counts)
+
+    def execute_batch_esp_vjp_device(self, positions, points, grad, esp_bar=None):
+        """The same on torch tensors (float64, on the kernel's device, contiguous): grad (B,P) is
+        overwritten (split_gradient gives its views).  Asynchronous on the kernel's stream."""
+        import torch
+        if not isinstance(positions, torch.Tensor):
+            raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
+        npts = self._check_esp_points(points, nconf, torch, torch.Tensor)
+        if esp_bar is not None and (not isinstance(esp_bar, torch.Tensor)
+                                    or self._check_batch_array(esp_bar, "esp_bar", (npts,), torch) != nconf):
+            raise ValueError(f"esp_bar must be a float64 Tensor for {nconf} conformations")
+        if not isinstance(grad, torch.Tensor):
+            raise ValueError("grad must be a torch tensor of shape (B, P)")
+        if self._check_batch_array(grad, "grad", (sum(self.param_counts()),), torch) != nconf:
+            raise ValueError(f"grad must hold {nconf} conformations")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _cabi.check(self._lib.cf_compute_batch_esp_vjp(self._h, nconf, ptr(positions), npts, ptr(points), ptr(esp_bar),
+                                                       ptr(grad)), self._lib)
+
     # Hessian-vector products of the batch (cf_compute_batch_hvp; boxes=: cf_compute_batch_periodic_hvp) --
     def _check_hvp_vectors(self, vectors, nconf, module, kind):
         if not isinstance(vectors, kind):

@@ -136,6 +136,24 @@ def cluster_c1(seed: int = SEED):
     return system, force, pos, None
 
 
+def probe_points(confs, npts: int, seed: int = SEED, grow: float = 0.3, rmin: float = 0.05):
+    """ESP probe points (B, npts, 3) for conformations (B, N, 3): seeded uniform draws in each
+    conformation's bounding box grown by `grow` nm; a draw closer than `rmin` nm to an atom is
+    redrawn.  Returns (points, the smallest point-atom distance)."""
+    rng = np.random.default_rng(seed)
+    out, closest = np.empty((len(confs), npts, 3)), np.inf
+    for b, x in enumerate(confs):
+        lo, hi = x.min(axis=0) - grow, x.max(axis=0) + grow
+        r = rng.uniform(lo, hi, size=(npts, 3))
+        while True:
+            d = np.sqrt(((r[:, None] - x[None]) ** 2).sum(axis=2)).min(axis=1)
+            if (d >= rmin).all():
+                break
+            r[d < rmin] = rng.uniform(lo, hi, size=(int((d < rmin).sum()), 3))
+        out[b], closest = r, min(closest, d.min())
+    return out, float(closest)
+
+
 def nacl_crystal(cells: int = 4, a: float = 0.5, cutoff: float = 1.0, ewald_tol: float = 1e-10):
     """Rock-salt crystal (Madelung known answer): cells^3 conventional cells, lattice a."""
     force = CoulForce()
