@@ -41,7 +41,8 @@ extern "C" {
                               cf_compute_batch_periodic_hvp_host; cf_compute_batch_periodic_virial,
                               cf_compute_batch_periodic_virial_host; cf_compute_batch_periodic_virial_vjp,
                               cf_compute_batch_periodic_virial_vjp_host; cf_compute_batch_esp,
-                              cf_compute_batch_esp_host, cf_compute_batch_esp_vjp, cf_compute_batch_esp_vjp_host */
+                              cf_compute_batch_esp_host, cf_compute_batch_esp_vjp, cf_compute_batch_esp_vjp_host;
+                              cf_compute_batch_hvp_vjp, cf_compute_batch_hvp_vjp_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -677,13 +678,72 @@ CF_EXPORT int cf_compute_batch_esp_vjp_host(cf_handle* h, int32_t nconf, const d
  * inputs and outputs must stay valid until the stream reaches them.  cf_get_batch_stats counts the
  * call, its nconf conformations and its passes; cf_compute's state and diagnostics are not touched; it
  * reads the parameter buffers cf_update_parameters last wrote.  No guard bits.  Out of scope: periodic
- * handles (cf_compute_batch_periodic_hvp below), the derivative of H with respect to the parameters.
+ * handles (cf_compute_batch_periodic_hvp below).  The derivative of H with respect to the parameters:
+ * cf_compute_batch_hvp_vjp, below.
  */
 CF_EXPORT int cf_compute_batch_hvp(cf_handle* h, int32_t nconf, const double* pos_dev, int32_t nvec,
                                    const double* vec_dev, double* out_dev);
 /* synchronous host-memory form of the same (H2D, evaluate, D2H) */
 CF_EXPORT int cf_compute_batch_hvp_host(cf_handle* h, int32_t nconf, const double* pos_host, int32_t nvec,
                                         const double* vec_host, double* out_host);
+/*
+ * Parameter gradients of those products: the reverse-mode product a loss on H v needs -- vibrational
+ * frequencies (first-order perturbation theory: d omega^2 / d theta = e^T (dH/dtheta) e for a
+ * mass-weighted normal mode e), projected Hessians, the harmonic check of a fitted model.  Per
+ * conformation c, with the cotangent
+ *   out_bar_dev [nconf][nvec][N][3] fp64 DEVICE, the cotangent of cf_compute_batch_hvp's out (NULL = zero),
+ * the scalar is   L_c = sum_k out_bar[c][k] . (H(x_c) v_ck),   H exactly the Hessian cf_compute_batch_hvp
+ * applies, and
+ *   grad_dev [nconf][P]   dL_c/d(base charges, flux parameters), OVERWRITTEN, rows in
+ *                         cf_get_param_counts order: base charges, bonds (k, b), angles (k, theta0),
+ *                         waters (k1, k2, kub, b0, ub0); one row per conformation, summed over its nvec
+ *                         directions and not over the conformations
+ *   pos_dev, vec_dev      as cf_compute_batch_hvp
+ * out_bar_dev == vec_dev is legal (both are read only): the frequency case out_bar = v.
+ * out_bar_dev == NULL: one memset of grad, the call and its conformations are counted, no pass.
+ * nvec = 0 with nconf > 0: the gradient of an empty sum is zero -- the same memset and counts, no pass
+ * (unlike cf_compute_batch_hvp, whose output is empty then, this call's output is not).
+ * Closed form.  The energy depends on these parameters only through the charges q after flux and is
+ * quadratic in them, and every flux piece is q_a += c_a k (gamma(x) - ref) with gamma a bond length, a
+ * water distance or an angle.  With u = out_bar and v = vec of one (conformation, direction), d = x_j -
+ * x_i, r = |d|, w^u = u_j - u_i, w^v = v_j - v_i, the sums over the non-excluded j != i (the forward
+ * pair set), and q^u = D_u q, q^v = D_v q, q^uv = D_u D_v q the directional derivatives of the charges:
+ *   g_i    = ke sum_j q_j / r
+ *   g^u_i  = ke sum_j [ q^u_j / r - q_j (d.w^u) / r^3 ]                          (g^v likewise)
+ *   g^uv_i = ke sum_j [ q^uv_j / r - (q^u_j (d.w^v) + q^v_j (d.w^u) + q_j (w^u.w^v)) / r^3
+ *                       + 3 q_j (d.w^u)(d.w^v) / r^5 ]
+ *   dL/d(base charge i) = sum_k g^uv_i
+ *   dL/dk   += sum_k sum_a c_a [ g^uv_a (gamma - ref) + g^u_a gamma^v + g^v_a gamma^u + g_a gamma^uv ]
+ *   dL/dref += -k sum_k sum_a c_a g^uv_a
+ * over the pieces of every term (a water's b0 collects from its r12 and r13 pieces, k1 and k2 cross
+ * over, as in cf_compute_batch_vjp).  gamma^u, gamma^v and gamma^uv come from the term geometry
+ * evaluated on second-order dual numbers (value, d/du, d/dv, d2/dudv).  LJ does not enter; neither
+ * dq/dx nor its tangent is needed.  Nothing divides by a parameter: a term with k = 0 is legal.
+ * A pass is conformations x directions by cf_compute_batch_hvp's rule and at most six kernel launches
+ * (flux terms, charges, geometry tangents, charge tangents, all pairs, gradient rows), in the workspace of cf_compute_batch plus,
+ * per (conformation, direction), 3 doubles per term geometry (one per bond and angle, three per
+ * water) and 7 N.  The pair kernel does what does not depend on the direction once for a chunk of 4
+ * directions of a conformation.  No atomics; every sum's order depends only on N, the topology and
+ * the order of the directions (ascending k, left to right; a conformation whose directions take several
+ * passes continues its sums from grad), so a conformation's row is bitwise the same alone, at any
+ * position of any batch, under any cf_set_batch_limit, however its directions are split into passes
+ * and in the host and the device form.
+ *
+ * Errors and states as cf_compute_batch_hvp: a periodic handle CF_ERR_INVALID; world_size > 1 or a
+ * call between cf_compute_begin and _end CF_ERR_STATE; NULL pos, vec or grad, nconf < 0 or nvec < 0
+ * CF_ERR_INVALID; nconf = 0 is a no-op that counts nothing; a NULL handle is rejected without touching
+ * a device; a guard bit already set fails the call.  Always fp64, eager launches on the handle's stream
+ * (never captured or replayed, not recorded by cf_set_timing), asynchronous.  cf_get_batch_stats counts
+ * the call, its nconf conformations and its passes; cf_compute's state and diagnostics are not touched;
+ * it reads the parameter buffers cf_update_parameters last wrote.  No guard bits.  Out of scope:
+ * periodic handles (the derivative of cf_compute_batch_periodic_hvp); LJ sigma / epsilon gradients of
+ * H; gradients with respect to positions or vectors; a special kernel for out_bar = v.
+ */
+CF_EXPORT int cf_compute_batch_hvp_vjp(cf_handle* h, int32_t nconf, const double* pos_dev, int32_t nvec,
+                                       const double* vec_dev, const double* out_bar_dev, double* grad_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_hvp_vjp_host(cf_handle* h, int32_t nconf, const double* pos_host, int32_t nvec,
+                                            const double* vec_host, const double* out_bar_host, double* grad_host);
 /*
  * Hessian-vector products of the periodic batch -- normal modes and phonons of ice and small liquid
  * boxes, Newton-CG relaxation of condensed-phase frames, the harmonic check of a fitted model on its
@@ -847,7 +907,9 @@ CF_EXPORT int cf_compute_batch_periodic_virial_vjp_host(cf_handle* h, int32_t nc
  * per conformation the doubles of cf_compute_batch, per (conformation, direction) S + 3 D + 3 N more
  * (S charge slots: 2 per bond, 3 per angle or water; D dq/dx entries: 4 per bond, 9 per angle or
  * water); the limit caps its conformations, and a conformation whose nvec directions alone exceed
- * 256 MiB or 65535 takes its directions in several passes.  cf_compute_batch_periodic_hvp: the same
+ * 256 MiB or 65535 takes its directions in several passes.  cf_compute_batch_hvp_vjp: the same rules
+ * with, per (conformation, direction), 3 G + 7 N doubles (G term geometries: 1 per bond or angle, 3 per
+ * water) in place of S + 3 D + 3 N.  cf_compute_batch_periodic_hvp: the same
  * rules with, per conformation, the doubles of cf_compute_batch_periodic and, per (conformation,
  * direction), S + 3 D + 3 N and 2 more per k-vector.  cf_compute_batch_periodic_virial: the
  * doubles of cf_compute_batch_periodic (its scratch is not counted).

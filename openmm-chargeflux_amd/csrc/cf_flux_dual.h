@@ -122,6 +122,69 @@ __device__ __forceinline__ void flux_term_nopbc(int type, const double* __restri
     }
 }
 
+// ---- second order: (value, d/du, d/dv, d2/dudv) along two directions u and v ------------------------
+// The hyper-dual number of the parameter gradients of the Hessian-vector products
+// (cf_kernels_batch_hvp_grad.hip; DESIGN.md §4.6, "batched, Hessian-vector parameter gradients").
+// With the atoms' positions carrying u and v as their first-order parts (uv = 0: the positions are
+// linear in both), a term's geometry comes out with its two directional derivatives and the mixed
+// second one.  A function f of one number: (f, f' a.u, f' a.v, f' a.uv + f'' a.u a.v).
+struct HDual {
+    double v, u, w, uw;   // value, along u, along v, mixed
+    __device__ __forceinline__ HDual() : v(0.0), u(0.0), w(0.0), uw(0.0) {}
+    __device__ __forceinline__ HDual(double v_) : v(v_), u(0.0), w(0.0), uw(0.0) {}
+    __device__ __forceinline__ HDual(double v_, double u_, double w_, double uw_) : v(v_), u(u_), w(w_), uw(uw_) {}
+};
+
+__device__ __forceinline__ HDual hd_chain(HDual a, double f, double f1, double f2) {
+    return HDual(f, f1 * a.u, f1 * a.w, f1 * a.uw + f2 * a.u * a.w);
+}
+__device__ __forceinline__ HDual operator+(HDual a, HDual b) { return HDual(a.v + b.v, a.u + b.u, a.w + b.w, a.uw + b.uw); }
+__device__ __forceinline__ HDual operator-(HDual a, HDual b) { return HDual(a.v - b.v, a.u - b.u, a.w - b.w, a.uw - b.uw); }
+__device__ __forceinline__ HDual operator*(HDual a, HDual b) {
+    return HDual(a.v * b.v, a.u * b.v + a.v * b.u, a.w * b.v + a.v * b.w,
+                 a.uw * b.v + a.u * b.w + a.w * b.u + a.v * b.uw);
+}
+__device__ __forceinline__ HDual operator/(HDual a, HDual b) {   // a * (1 / b): f = 1/b, f' = -f^2, f'' = 2 f^3
+    const double f = 1.0 / b.v;
+    return a * hd_chain(b, f, -f * f, 2 * f * f * f);
+}
+__device__ __forceinline__ HDual operator/(HDual a, double b) { return HDual(a.v / b, a.u / b, a.w / b, a.uw / b); }
+__device__ __forceinline__ HDual num_sqrt(HDual a) {   // f' = 1 / (2 s), f'' = -f' / (2 a)
+    const double s = sqrt(a.v), f1 = 0.5 / s;
+    return hd_chain(a, s, f1, -0.5 * f1 / a.v);
+}
+__device__ __forceinline__ HDual num_acos(HDual a) {   // f' = -1 / sqrt(1 - a^2), f'' = f' a / (1 - a^2)
+    const double o = 1 - a.v * a.v, f1 = -1.0 / sqrt(o);
+    return hd_chain(a, acos(a.v), f1, f1 * a.v / o);
+}
+
+// The geometry of one flux term without a box, flux_term_nopbc's expressions: gam[0] of a bond is
+// r12 and of an angle theta, gam[0..3) of a water (r12, r13, r23); the rest is left alone.  Every
+// charge delta of the term is c k (gam - ref) for one of these.
+template <class T>
+__device__ __forceinline__ void term_gammas(int type, const T x1[3], const T x2[3], const T x3[3], T gam[3]) {
+    if (type == 0) {
+        T d[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) d[j] = x2[j] - x1[j];
+        gam[0] = num_sqrt(num_dot(d, d));
+    } else if (type == 1) {
+        T d21[3], d23[3], d13[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) { d21[j] = x1[j] - x2[j]; d23[j] = x3[j] - x2[j]; d13[j] = x3[j] - x1[j]; }
+        const T r21_2 = num_dot(d21, d21), r23_2 = num_dot(d23, d23), r13_2 = num_dot(d13, d13);
+        const T r21 = num_sqrt(r21_2), r23 = num_sqrt(r23_2);
+        gam[0] = num_acos((r23_2 + r21_2 - r13_2) / 2.0 / r21 / r23);
+    } else {
+        T d12[3], d13[3], d23[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) { d12[j] = x2[j] - x1[j]; d13[j] = x3[j] - x1[j]; d23[j] = x3[j] - x2[j]; }
+        gam[0] = num_sqrt(num_dot(d12, d12));
+        gam[1] = num_sqrt(num_dot(d13, d13));
+        gam[2] = num_sqrt(num_dot(d23, d23));
+    }
+}
+
 // delta_r (cf_pair.h: b - a, minimum image in the reduced box L, T) under one name for both number
 // types.  The image shift is piecewise constant in the positions, so a Dual's value is delta_r of
 // the values and its tangent the plain difference of the tangents.

@@ -512,6 +512,28 @@ void batch_hvp_carve(const Handle& h, double* base, int cap, BatchHvpWs& w);
 void launch_batch_hvp(Handle& h, const BatchWs& w, const BatchHvpWs& hw, int nconf, int kv, const double* pos,
                       const double* vec, long vstride, double* out);
 
+// parameter gradients of those products (cf_kernels_batch_hvp_grad.hip, cf_compute_batch_hvp_vjp): the
+// extra workspace of one pass beside BatchWs, one row per (conformation, direction) of the pass, carved
+// from one allocation of cap * batch_hvp_grad_doubles_per_row doubles.  G = nb + na + 3 nw term
+// geometries (a bond's length, an angle, a water's three distances).  No dq/dx or Ddot block.
+struct BatchHvpGradWs {
+    double* base = nullptr;
+    int cap = 0;                // rows the arrays hold
+    double* gam = nullptr;      // [cap][3][G] the geometries' tangents along u, along v and the mixed one
+    double* qt = nullptr;       // [cap][3][N] the charges' tangents q^u, q^v, q^uv
+    double* gt = nullptr;       // [cap][3][N] g^u, g^v, g^uv
+    double* g = nullptr;        // [cap][N] dE/dq, a row per CONFORMATION of the pass (never more than rows)
+};
+size_t batch_hvp_grad_doubles_per_row(const Handle& h);
+void batch_hvp_grad_carve(const Handle& h, double* base, int cap, BatchHvpGradWs& w);
+int batch_hvp_grad_chunk();     // directions a block of the pair kernel carries (build-time)
+// one pass of nconf <= w.cap conformations x kv directions (nconf * kv <= min(gw.cap, kBatchMaxPass)
+// rows) on h.stream: at most six launches.  pos [nconf][N][3]; vec and out_bar: direction k of
+// conformation c at c * vstride + k * 3 N doubles (they may be the same array); grad [nconf][N + 2 nb +
+// 2 na + 5 nw]: overwritten when first, else the pass's rows are added to it in ascending k
+void launch_batch_hvp_vjp(Handle& h, const BatchWs& w, const BatchHvpGradWs& gw, int nconf, int kv, const double* pos,
+                          const double* vec, const double* out_bar, long vstride, bool first, double* grad);
+
 // Hessian-vector products of the periodic batch (cf_kernels_batch_pbc_hvp.hip,
 // cf_compute_batch_periodic_hvp): the extra workspace of one pass beside BatchPbcWs, one row per
 // (conformation, direction) of the pass, carved from one allocation of cap *

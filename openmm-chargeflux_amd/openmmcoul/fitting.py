@@ -41,6 +41,13 @@ the atomic polar tensors apts[c, b, i, j] = d mu_i / d x_bj, charge-flux part in
 esp() is cf_compute_batch_esp forward and one cf_compute_batch_esp_vjp backward: the potential
 V_p = ke sum_a q_a / |r_p - x_a| of the charges after flux at M probe points per conformation.
 
+    products = model.hvp(q, bonds, angles, waters, positions, vectors)    # non-periodic: (B,K,N,3)
+    loss = (((vectors * products).sum(dim=(2, 3)) - target) ** 2).sum()   # e . H e: squared frequencies
+    loss.backward()
+
+hvp() is cf_compute_batch_hvp forward and one cf_compute_batch_hvp_vjp backward: the Hessian-vector
+products H(x_b) v_bk and their closed-form parameter gradients.
+
 Convention (cf_compute_batch_lj_vjp): an atom with epsilon = 0 receives exactly 0 for its sigma and
 epsilon gradients.  The true derivative of sqrt(eps_i eps_j) is singular there; such an atom has no
 LJ interaction, and an optimiser leaves it at 0.
@@ -248,6 +255,42 @@ class _EspFn(torch.autograd.Function):
         return (None, *out, None, None)
 
 
+class _HvpFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, charges, bonds, angles, waters, positions, vectors):
+        params = tuple(t.detach().to("cpu", torch.float64).contiguous() for t in (charges, bonds, angles, waters))
+        model._load(params)
+        k = model.kernel
+        model._before()
+        out = k.execute_batch_hvp_device(positions, vectors)
+        model._after()
+        ctx.model, ctx.params, ctx.loaded = model, params, model._loads
+        ctx.inputs = (charges, bonds, angles, waters)
+        ctx.save_for_backward(positions, vectors)
+        return out
+
+    @staticmethod
+    def backward(ctx, out_bar):
+        model = ctx.model
+        k = model.kernel
+        positions, vectors = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[1:5]):
+            return (None,) * 7
+        if model._loads != ctx.loaded:   # another forward has changed the parameters since: put these back
+            model._load(ctx.params)
+            ctx.loaded = model._loads
+        cot = out_bar.detach().to(torch.float64).contiguous()
+        counts = k.param_counts()
+        grad = torch.empty((positions.shape[0], sum(counts)), dtype=torch.float64, device=positions.device)
+        model._before()
+        k.execute_batch_hvp_vjp_device(positions, vectors, grad, cot)
+        model._after()
+        g = k.split_gradient(grad.sum(dim=0, keepdim=True), counts)
+        out = [g[name][0].reshape(t.shape).to(t.device) if need else None
+               for t, name, need in zip(ctx.inputs, ("charges", "bonds", "angles", "waters"), ctx.needs_input_grad[1:5])]
+        return (None, *out, None, None)
+
+
 class BatchedChargeFlux:
     """Energies, forces and charges of B conformations as a differentiable function of the
     parameters.  kernel: a HipCalcCoulForceKernel initialised with `force` (one rank);
@@ -378,3 +421,20 @@ class BatchedChargeFlux:
         if points.dim() != 3 or points.shape[0] != positions.shape[0] or points.shape[2] != 3:   # before the parameters are loaded
             raise ValueError(f"points must have shape (B, M, 3), got {tuple(points.shape)}")
         return _EspFn.apply(self, charges, bonds, angles, waters, positions, points)
+
+    def hvp(self, charges, bonds, angles, waters, positions, vectors):
+        """Hessian-vector products H(x_b) v_bk (B,K,N,3) of B conformations of a non-periodic system
+        along the directions vectors (B,K,N,3) (float64, contiguous on the kernel's device) as a
+        differentiable function of the four parameter tensors (arguments as __call__;
+        cf_compute_batch_hvp forward, one cf_compute_batch_hvp_vjp with the incoming cotangent, summed
+        over the conformations, in backward).  With v a normal mode e, d(e . H e)/d(parameters) is the
+        first-order shift of its squared frequency.  Neither positions nor vectors may require grad."""
+        for t, name in ((charges, "charges"), (bonds, "bonds"), (angles, "angles"), (waters, "waters"),
+                        (positions, "positions"), (vectors, "vectors")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise ValueError(f"{name} must be a float64 torch tensor")
+        if positions.requires_grad or vectors.requires_grad:
+            raise ValueError("positions and vectors must not require grad: gradients with respect to them are not computed")
+        if vectors.dim() != 4 or vectors.shape[0] != positions.shape[0] or tuple(vectors.shape[2:]) != tuple(positions.shape[1:]):   # before the parameters are loaded
+            raise ValueError(f"vectors must have shape (B, K, N, 3), got {tuple(vectors.shape)}")
+        return _HvpFn.apply(self, charges, bonds, angles, waters, positions, vectors)

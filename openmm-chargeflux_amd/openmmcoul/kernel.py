@@ -761,6 +761,46 @@ class HipCalcCoulForceKernel:
                     self._lib)
         return out
 
+    def _check_hvp_cotangent(self, out_bar, nconf, nvec, module, kind):
+        if out_bar is not None and (not isinstance(out_bar, kind) or self._check_batch_array(
+                out_bar, "out_bar", (nvec, self._n, 3), module) != nconf):
+            raise ValueError(f"out_bar must be a float64 {kind.__name__} shaped like vectors")
+
+    def execute_batch_hvp_vjp_host(self, positions, vectors, out_bar=None):
+        """Gradients of L = sum_k out_bar_k . (H v_k) with respect to the base charges and the flux
+        parameters, per conformation (cf_compute_batch_hvp_vjp_host; non-periodic systems), H v the
+        products execute_batch_hvp_host returns.  positions (B,N,3), vectors (B,K,N,3), out_bar
+        (B,K,N,3): C-contiguous float64 numpy arrays; out_bar may be None (= zero) or vectors itself.
+        Returns the dict of execute_batch_vjp_host (split_gradient)."""
+        if not isinstance(positions, np.ndarray):
+            raise ValueError("positions must be a numpy array of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3))
+        nvec = self._check_hvp_vectors(vectors, nconf, np, np.ndarray)
+        self._check_hvp_cotangent(out_bar, nconf, nvec, np, np.ndarray)
+        counts = self.param_counts()
+        flat = np.zeros((nconf, sum(counts)))
+        _cabi.check(self._lib.cf_compute_batch_hvp_vjp_host(self._h, nconf, _dp(positions), nvec, _dp(vectors),
+                                                            _dp(out_bar) if out_bar is not None else None,
+                                                            _dp(flat)), self._lib)
+        return self.split_gradient(flat, counts)
+
+    def execute_batch_hvp_vjp_device(self, positions, vectors, grad, out_bar=None):
+        """The same on torch tensors (float64, on the kernel's device, contiguous): grad (B,P) is
+        overwritten (split_gradient gives its views).  Asynchronous on the kernel's stream."""
+        import torch
+        if not isinstance(positions, torch.Tensor):
+            raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
+        nconf = self._check_batch_array(positions, "positions", (self._n, 3), torch)
+        nvec = self._check_hvp_vectors(vectors, nconf, torch, torch.Tensor)
+        self._check_hvp_cotangent(out_bar, nconf, nvec, torch, torch.Tensor)
+        if not isinstance(grad, torch.Tensor):
+            raise ValueError("grad must be a torch tensor of shape (B, P)")
+        if self._check_batch_array(grad, "grad", (sum(self.param_counts()),), torch) != nconf:
+            raise ValueError(f"grad must hold {nconf} conformations")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _cabi.check(self._lib.cf_compute_batch_hvp_vjp(self._h, nconf, ptr(positions), nvec, ptr(vectors), ptr(out_bar),
+                                                       ptr(grad)), self._lib)
+
     def hessians_host(self, positions, symmetrize=True, *, boxes=None):
         """Full Hessians (B,3N,3N) of B conformations: one execute_batch_hvp_host call with the 3N unit
         vectors per conformation, symmetrised as (H + H^T) / 2 (symmetrize=False: the products as they
