@@ -42,7 +42,8 @@ extern "C" {
                               cf_compute_batch_periodic_virial_host; cf_compute_batch_periodic_virial_vjp,
                               cf_compute_batch_periodic_virial_vjp_host; cf_compute_batch_esp,
                               cf_compute_batch_esp_host, cf_compute_batch_esp_vjp, cf_compute_batch_esp_vjp_host;
-                              cf_compute_batch_hvp_vjp, cf_compute_batch_hvp_vjp_host */
+                              cf_compute_batch_hvp_vjp, cf_compute_batch_hvp_vjp_host;
+                              cf_compute_batch_periodic_hvp_vjp, cf_compute_batch_periodic_hvp_vjp_host */
 
 /* Error codes (negative).  cf_last_error() returns the message of the last failure
  * on the calling thread.  Mirrors the reference's OpenMMException paths. */
@@ -735,8 +736,8 @@ CF_EXPORT int cf_compute_batch_hvp_host(cf_handle* h, int32_t nconf, const doubl
  * a device; a guard bit already set fails the call.  Always fp64, eager launches on the handle's stream
  * (never captured or replayed, not recorded by cf_set_timing), asynchronous.  cf_get_batch_stats counts
  * the call, its nconf conformations and its passes; cf_compute's state and diagnostics are not touched;
- * it reads the parameter buffers cf_update_parameters last wrote.  No guard bits.  Out of scope:
- * periodic handles (the derivative of cf_compute_batch_periodic_hvp); LJ sigma / epsilon gradients of
+ * it reads the parameter buffers cf_update_parameters last wrote.  No guard bits.  Periodic handles:
+ * cf_compute_batch_periodic_hvp_vjp, below.  Out of scope: LJ sigma / epsilon gradients of
  * H; gradients with respect to positions or vectors; a special kernel for out_bar = v.
  */
 CF_EXPORT int cf_compute_batch_hvp_vjp(cf_handle* h, int32_t nconf, const double* pos_dev, int32_t nvec,
@@ -795,9 +796,10 @@ CF_EXPORT int cf_compute_batch_hvp_vjp_host(cf_handle* h, int32_t nconf, const d
  * fp64, eager launches on the handle's stream (never captured or replayed, not recorded by
  * cf_set_timing), asynchronous.  cf_get_batch_stats counts the call, its nconf conformations and its
  * passes; cf_compute's state and diagnostics are not touched, and the forward periodic batch and both
- * periodic VJPs return the same bits before and after.  No guard bits.  Out of scope: the derivative
+ * periodic VJPs return the same bits before and after.  No guard bits.  The derivative of H with
+ * respect to the parameters: cf_compute_batch_periodic_hvp_vjp, below.  Out of scope: the derivative
  * of H with respect to the box (elastic constants; the virial of a frame is
- * cf_compute_batch_periodic_virial's) and with respect to the parameters.
+ * cf_compute_batch_periodic_virial's).
  */
 CF_EXPORT int cf_compute_batch_periodic_hvp(cf_handle* h, int32_t nconf, const double* pos_dev,
                                             const double* boxes_host, int32_t nvec, const double* vec_dev,
@@ -806,6 +808,72 @@ CF_EXPORT int cf_compute_batch_periodic_hvp(cf_handle* h, int32_t nconf, const d
 CF_EXPORT int cf_compute_batch_periodic_hvp_host(cf_handle* h, int32_t nconf, const double* pos_host,
                                                  const double* boxes_host, int32_t nvec, const double* vec_host,
                                                  double* out_host);
+/*
+ * Parameter gradients of those periodic products -- fits to condensed-phase vibrational data: ice
+ * phonons, librational bands of small liquid boxes, projected Hessians of NVT / NPT frames.  Per
+ * conformation c with its box:
+ *   L_c = sum_k out_bar[c][k] . (H(x_c; box_c) v_ck),   H exactly the Hessian
+ * cf_compute_batch_periodic_hvp applies: fixed box, pair set and image of every pair, the erfc pairs
+ * within the cutoff, the erf correction of every excluded pair at any distance, the self term, the
+ * exact half-space k-sum with k from the box diagonals, cf_create's alpha and kmax, the handle's
+ * one_4pi_eps0.  Triclinic frames are accepted, as in the forward call.
+ *   pos_dev, vec_dev, out_bar_dev   as cf_compute_batch_hvp_vjp (out_bar may be vec itself, or NULL = zero)
+ *   boxes_host                      as cf_compute_batch_periodic_hvp
+ *   grad_dev [nconf][P]             rows in cf_get_param_counts order, OVERWRITTEN: each conformation's
+ *                                   row summed over its directions, never across conformations
+ * Closed form.  E = E_LJ + q^T M(x) q / 2 with M the pair, self and reciprocal parts, g = M q; with
+ * u = out_bar, v = vec and gamma a term's MINIMUM-IMAGE geometry on hyper-dual numbers (the image shift
+ * is piecewise constant: the value is the minimum image of the values, every tangent the plain
+ * difference of the atoms' tangents) the assembly is cf_compute_batch_hvp_vjp's:
+ *   dL/d(base charge i) = sum_k g^uv_i
+ *   dL/dk   += sum_k sum_a c_a [ g^uv_a (gamma - ref) + g^u_a gamma^v + g^v_a gamma^u + g_a gamma^uv ]
+ *   dL/dref += -k sum_k sum_a c_a g^uv_a
+ * With d the minimum image of x_i - x_j, r = |d|, w^u = u_i - u_j, c = 2 / sqrt(pi), c_s = ke alpha /
+ * sqrt(pi), P = erfc(alpha r) for a non-excluded pair within the cutoff and -erf(alpha r) for an excluded
+ * pair at any distance, Q = P + c alpha r e^{-alpha^2 r^2}, T = c (alpha r)^3 e^{-alpha^2 r^2}:
+ *   g_i    = ke sum_j q_j P / r - 2 c_s q_i
+ *   g^u_i  = ke sum_j [ q^u_j P / r - q_j Q (d.w^u) / r^3 ] - 2 c_s q^u_i               (g^v likewise)
+ *   g^uv_i = ke sum_j [ q^uv_j P / r - Q (q^u_j (d.w^v) + q^v_j (d.w^u) + q_j (w^u.w^v)) / r^3
+ *                       + q_j (3 Q + 2 T) (d.w^u)(d.w^v) / r^5 ] - 2 c_s q^uv_i
+ * (Q = 1, T = 0, P = 1: the non-periodic formulas) plus the reciprocal part, with e_i = e^{i k.x_i},
+ * kappa^u_i = k.u_i and A_k = 2 c_k S(k) over the forward path's half-space k set:
+ *   S    = sum_j q_j e_j
+ *   S^u  = sum_j (q^u_j + i q_j kappa^u_j) e_j                                  (S^v likewise)
+ *   S^uv = sum_j (q^uv_j + i (q^u_j kappa^v_j + q^v_j kappa^u_j) - q_j kappa^u_j kappa^v_j) e_j
+ *   g_i    += sum_k Re[ conj(e_i) A ]
+ *   g^u_i  += sum_k Re[ conj(e_i) (A^u - i kappa^u_i A) ]
+ *   g^uv_i += sum_k Re[ conj(e_i) (A^uv - i kappa^u_i A^v - i kappa^v_i A^u - kappa^u_i kappa^v_i A) ]
+ * LJ does not enter; neither dq/dx nor its tangent is needed; nothing divides by a parameter, so a
+ * term with k = 0 is legal.
+ * The work per pair and per (atom, k) that does not depend on the direction is done once for a chunk
+ * of 4 direction rows of a conformation.  A pass is at most nine launches (flux terms, charges, phase
+ * tables, geometry tangents, charge tangents, structure factors, pairs, reciprocal part, gradient
+ * rows), pass sizes as cf_compute_batch_hvp_vjp with the periodic workspace (cf_set_batch_limit); a
+ * conformation whose directions take several passes continues its running sums from grad.  No
+ * atomics; every sum's order depends only on N, the topology, kmax and the order of the directions, so
+ * a conformation's row is bitwise the same alone, at any position of any batch, in any slot of a
+ * chunk, under any cf_set_batch_limit, however its directions are split into passes and in the host
+ * and the device form.
+ *
+ * Errors and states as cf_compute_batch_periodic_hvp: a non-periodic handle CF_ERR_INVALID; a bad
+ * box CF_ERR_INVALID naming the conformation, before anything is launched or counted; world_size > 1
+ * or a call between cf_compute_begin and _end CF_ERR_STATE; NULL pos, boxes, vec or grad, nconf < 0 or
+ * nvec < 0 CF_ERR_INVALID; a NULL handle is rejected without touching a device; a guard bit already
+ * set fails the call.  nconf = 0 is a no-op that counts nothing; out_bar = NULL, or nvec = 0 with
+ * nconf > 0, does one memset of grad and counts the call and its conformations, and no pass.  Always
+ * fp64, eager launches on the handle's stream (never captured or replayed, not recorded by
+ * cf_set_timing), asynchronous.  cf_compute's state and the other batch calls' results are not
+ * touched; it reads the parameter buffers cf_update_parameters last wrote.  No guard bits.  Out of
+ * scope: LJ sigma / epsilon gradients of H; box (strain) derivatives of H; gradients with respect to
+ * positions or vectors; a special kernel for out_bar = v.
+ */
+CF_EXPORT int cf_compute_batch_periodic_hvp_vjp(cf_handle* h, int32_t nconf, const double* pos_dev,
+                                                const double* boxes_host, int32_t nvec, const double* vec_dev,
+                                                const double* out_bar_dev, double* grad_dev);
+/* synchronous host-memory form of the same (H2D, evaluate, D2H) */
+CF_EXPORT int cf_compute_batch_periodic_hvp_vjp_host(cf_handle* h, int32_t nconf, const double* pos_host,
+                                                     const double* boxes_host, int32_t nvec, const double* vec_host,
+                                                     const double* out_bar_host, double* grad_host);
 /*
  * cf_compute_batch_periodic with the virial tensor of every frame: the third training and validation
  * label of NVT / NPT frames beside energy and forces (pressure, cell relaxation, NPT density).
@@ -911,7 +979,9 @@ CF_EXPORT int cf_compute_batch_periodic_virial_vjp_host(cf_handle* h, int32_t nc
  * with, per (conformation, direction), 3 G + 7 N doubles (G term geometries: 1 per bond or angle, 3 per
  * water) in place of S + 3 D + 3 N.  cf_compute_batch_periodic_hvp: the same
  * rules with, per conformation, the doubles of cf_compute_batch_periodic and, per (conformation,
- * direction), S + 3 D + 3 N and 2 more per k-vector.  cf_compute_batch_periodic_virial: the
+ * direction), S + 3 D + 3 N and 2 more per k-vector.  cf_compute_batch_periodic_hvp_vjp: those
+ * per-conformation doubles and, per (conformation, direction), 3 per term geometry, 7 N and 6 per
+ * k-vector.  cf_compute_batch_periodic_virial: the
  * doubles of cf_compute_batch_periodic (its scratch is not counted).
  * cf_compute_batch_periodic_virial_vjp: the doubles of cf_compute_batch_periodic and qdot[N], g[N],
  * a[N], 2 more doubles per k-vector and the 6 of T.  A

@@ -106,6 +106,9 @@ struct cf_handle {
     // cf_compute_batch_hvp_vjp: the extra workspace beside `batch`, a row per (conformation, direction)
     // of a pass (in H->allocs); its host form stages through batch_hvp_stage
     cf::BatchHvpGradWs batch_hvp_grad;
+    // cf_compute_batch_periodic_hvp_vjp: the extra workspace beside `batch_pbc`, a row per (conformation,
+    // direction) of a pass (in H->allocs); its host form stages through batch_hvp_stage
+    cf::BatchPbcHvpGradWs batch_pbc_hvp_grad;
     // cf_compute_batch_periodic_virial: the tensor sums' scratch beside `batch_pbc` and the host form's
     // staging of the tensors [confs][9] (its other arrays go through batch_stage); both in H->allocs
     cf::BatchPbcVirialWs batch_pbc_virial;
@@ -3117,6 +3120,95 @@ CF_EXPORT int cf_compute_batch_periodic_hvp_host(cf_handle* H, int32_t nconf, co
                          [&](const double* pos, const double* vec, double* out) {
                              return cf_compute_batch_periodic_hvp(H, nconf, pos, boxes_host, nvec, vec, out);
                          });
+    });
+}
+
+// ---- parameter gradients of those products (cf_kernels_batch_pbc_hvp_grad.hip) -----------------------
+CF_EXPORT int cf_compute_batch_periodic_hvp_vjp(cf_handle* H, int32_t nconf, const double* pos_dev,
+                                                const double* boxes_host, int32_t nvec, const double* vec_dev,
+                                                const double* out_bar_dev, double* grad_dev) {
+    return guarded([&] {
+        batch_periodic_hvp_precheck(H, nconf, pos_dev, boxes_host, nvec, vec_dev, grad_dev,
+                                    "cf_compute_batch_periodic_hvp_vjp", "cf_compute_batch_hvp_vjp");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+        H->batch_calls++;
+        H->batch_confs += nconf;
+        if (!out_bar_dev || nvec == 0) {   // a zero cotangent, or the empty sum: exact zeros, no pass
+            check_hip(hipMemsetAsync(grad_dev, 0, sizeof(double) * np * (size_t)nconf, h.stream), "memset grad");
+            return;
+        }
+        // the pass sizes of cf_compute_batch_hvp_vjp with the periodic workspaces
+        int pass = 0, kv = 0;
+        hvp_pass_size(H, cf::batch_pbc_doubles_per_conf(h) * sizeof(double),
+                      cf::batch_pbc_hvp_grad_doubles_per_row(h) * sizeof(double), nconf, nvec, pass, kv);
+        if (pass > H->batch_pbc.cap) {   // first call or growth: allocates (and so synchronises)
+            double* old = H->batch_pbc.base;
+            H->batch_pbc = cf::BatchPbcWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_pbc_doubles_per_conf(h) * (size_t)pass);
+            cf::batch_pbc_carve(h, base, pass, H->batch_pbc);
+        }
+        if (pass * kv > H->batch_pbc_hvp_grad.cap) {
+            double* old = H->batch_pbc_hvp_grad.base;
+            H->batch_pbc_hvp_grad = cf::BatchPbcHvpGradWs();
+            dfree(H, old);
+            double* base = dalloc<double>(H, cf::batch_pbc_hvp_grad_doubles_per_row(h) * (size_t)pass * (size_t)kv);
+            cf::batch_pbc_hvp_grad_carve(h, base, pass * kv, H->batch_pbc_hvp_grad);
+        }
+        batch_boxes_upload(H, nconf, boxes_host);
+        // eager launches on the handle's stream, never captured or replayed and not bracketed by the
+        // per-phase timing events (as cf_compute_batch_periodic).  The first pass over a conformation's
+        // directions overwrites its row of grad, the later ones continue its sums
+        const size_t vstride = 3 * n * (size_t)nvec;
+        for (int c0 = 0; c0 < nconf; c0 += pass) {
+            const int m = std::min(pass, nconf - c0);
+            for (int k0 = 0; k0 < nvec; k0 += kv) {
+                const size_t at = vstride * (size_t)c0 + 3 * n * (size_t)k0;
+                cf::launch_batch_pbc_hvp_vjp(h, H->batch_pbc, H->batch_pbc_hvp_grad, m, std::min(kv, nvec - k0),
+                                             pos_dev + 3 * n * c0, H->batch_boxes_dev + 8 * (size_t)c0, vec_dev + at,
+                                             out_bar_dev + at, (long)vstride, k0 == 0, grad_dev + np * c0);
+                H->batch_passes++;
+            }
+        }
+        launch_check(h, "compute_batch_periodic_hvp_vjp");
+    });
+}
+
+// synchronous host form, cf_compute_batch_hvp_vjp_host's staging (a cotangent that IS the directions
+// array goes up once)
+CF_EXPORT int cf_compute_batch_periodic_hvp_vjp_host(cf_handle* H, int32_t nconf, const double* pos_host,
+                                                     const double* boxes_host, int32_t nvec, const double* vec_host,
+                                                     const double* out_bar_host, double* grad_host) {
+    return guarded([&] {
+        batch_periodic_hvp_precheck(H, nconf, pos_host, boxes_host, nvec, vec_host, grad_host,
+                                    "cf_compute_batch_periodic_hvp_vjp_host", "cf_compute_batch_hvp_vjp_host");
+        if (nconf == 0) return;
+        cf::Handle& h = H->h;
+        check_hip(hipSetDevice(h.device), "hipSetDevice");
+        const size_t n = (size_t)h.n, B = (size_t)nconf, K = (size_t)nvec;
+        const size_t np = n + 2 * (size_t)h.nb + 2 * (size_t)h.na + 5 * (size_t)h.nw;
+        const bool own_bar = out_bar_host && out_bar_host != vec_host;
+        double* pos = batch_hvp_stage(H, 3 * n * B * (1 + (own_bar ? 2 : 1) * K) + np * B);
+        double* vec = pos + 3 * n * B;
+        double* bar = own_bar ? vec + 3 * n * B * K : vec;
+        double* grad = vec + 3 * n * B * K * (own_bar ? 2 : 1);
+        check_hip(hipMemcpyAsync(pos, pos_host, sizeof(double) * 3 * n * B, hipMemcpyHostToDevice, h.stream),
+                  "H2D positions");
+        if (K > 0 && out_bar_host) {
+            check_hip(hipMemcpyAsync(vec, vec_host, sizeof(double) * 3 * n * B * K, hipMemcpyHostToDevice, h.stream),
+                      "H2D directions");
+            if (own_bar)
+                check_hip(hipMemcpyAsync(bar, out_bar_host, sizeof(double) * 3 * n * B * K, hipMemcpyHostToDevice,
+                                         h.stream), "H2D product cotangent");
+        }
+        const int rc = cf_compute_batch_periodic_hvp_vjp(H, nconf, pos, boxes_host, nvec, vec,
+                                                         out_bar_host ? bar : nullptr, grad);
+        if (rc != CF_OK) throw CfError(rc, g_err);
+        check_hip(hipMemcpyAsync(grad_host, grad, sizeof(double) * np * B, hipMemcpyDeviceToHost, h.stream), "D2H grad");
+        check_hip(hipStreamSynchronize(h.stream), "sync");
     });
 }
 

@@ -185,6 +185,9 @@ __device__ __forceinline__ void term_gammas(int type, const T x1[3], const T x2[
     }
 }
 
+// first geometry of term t: bonds and angles have one, waters three
+__device__ __forceinline__ int geom_start(int t, int nb, int na) { return t < nb + na ? t : nb + na + 3 * (t - nb - na); }
+
 // delta_r (cf_pair.h: b - a, minimum image in the reduced box L, T) under one name for both number
 // types.  The image shift is piecewise constant in the positions, so a Dual's value is delta_r of
 // the values and its tangent the plain difference of the tangents.
@@ -195,6 +198,37 @@ __device__ __forceinline__ void num_delta(const double a[3], const double b[3], 
 __device__ __forceinline__ void num_delta(const Dual a[3], const Dual b[3], double3 L, double3 T, Dual out[3]) {
     const double3 d = delta_r(make_double3(a[0].v, a[1].v, a[2].v), make_double3(b[0].v, b[1].v, b[2].v), L, 1, T);
     out[0] = Dual(d.x, b[0].d - a[0].d); out[1] = Dual(d.y, b[1].d - a[1].d); out[2] = Dual(d.z, b[2].d - a[2].d);
+}
+
+__device__ __forceinline__ void num_delta(const HDual a[3], const HDual b[3], double3 L, double3 T, HDual out[3]) {
+    const double3 d = delta_r(make_double3(a[0].v, a[1].v, a[2].v), make_double3(b[0].v, b[1].v, b[2].v), L, 1, T);
+    out[0] = HDual(d.x, b[0].u - a[0].u, b[0].w - a[0].w, b[0].uw - a[0].uw);
+    out[1] = HDual(d.y, b[1].u - a[1].u, b[1].w - a[1].w, b[1].uw - a[1].uw);
+    out[2] = HDual(d.z, b[2].u - a[2].u, b[2].w - a[2].w, b[2].uw - a[2].uw);
+}
+
+// term_gammas in a box: every difference vector the minimum image in (L, Tb), the delta_r calls of
+// flux_term_pbc below in its order and with its arguments (cf_kernels_batch_pbc_hvp_grad.hip).
+template <class T>
+__device__ __forceinline__ void term_gammas_pbc(int type, const T x1[3], const T x2[3], const T x3[3], double3 L,
+                                                double3 Tb, T gam[3]) {
+    if (type == 0) {
+        T d[3];
+        num_delta(x1, x2, L, Tb, d);
+        gam[0] = num_sqrt(num_dot(d, d));
+    } else if (type == 1) {
+        T d21[3], d23[3], d13[3];
+        num_delta(x2, x1, L, Tb, d21); num_delta(x2, x3, L, Tb, d23); num_delta(x1, x3, L, Tb, d13);
+        const T r21_2 = num_dot(d21, d21), r23_2 = num_dot(d23, d23), r13_2 = num_dot(d13, d13);
+        const T r21 = num_sqrt(r21_2), r23 = num_sqrt(r23_2);
+        gam[0] = num_acos((r23_2 + r21_2 - r13_2) / 2.0 / r21 / r23);
+    } else {
+        T d12[3], d13[3], d23[3];
+        num_delta(x1, x2, L, Tb, d12); num_delta(x1, x3, L, Tb, d13); num_delta(x2, x3, L, Tb, d23);
+        gam[0] = num_sqrt(num_dot(d12, d12));
+        gam[1] = num_sqrt(num_dot(d13, d13));
+        gam[2] = num_sqrt(num_dot(d23, d23));
+    }
 }
 
 // The periodic branch of flux_term (pbc = 1) over a number type T: flux_term_nopbc with every

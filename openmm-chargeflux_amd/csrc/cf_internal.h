@@ -557,6 +557,30 @@ int batch_pbc_hvp_chunk();      // directions a block of the pair / k-space kern
 void launch_batch_pbc_hvp(Handle& h, const BatchPbcWs& w, const BatchPbcHvpWs& hw, int nconf, int kv, const double* pos,
                           const double* boxes, const double* vec, long vstride, double* out);
 
+// parameter gradients of those periodic products (cf_kernels_batch_pbc_hvp_grad.hip,
+// cf_compute_batch_periodic_hvp_vjp): the extra workspace of one pass beside BatchPbcWs, one row per
+// (conformation, direction) of the pass, carved from one allocation of cap *
+// batch_pbc_hvp_grad_doubles_per_row doubles (the double2 array first: 16-B aligned).  G as BatchHvpGradWs.
+struct BatchPbcHvpGradWs {
+    double* base = nullptr;
+    int cap = 0;                // rows the arrays hold
+    double2* coeft = nullptr;   // [cap][3][khalf] 2 c_k (S^u, S^v, S^uv): the structure factor's tangents
+    double* gam = nullptr;      // [cap][3][G] the minimum-image geometries' tangents along u, along v, mixed
+    double* qt = nullptr;       // [cap][3][N] the charges' tangents q^u, q^v, q^uv
+    double* gt = nullptr;       // [cap][3][N] g^u, g^v, g^uv
+    double* g = nullptr;        // [cap][N] dE/dq, a row per CONFORMATION of the pass (never more than rows)
+};
+size_t batch_pbc_hvp_grad_doubles_per_row(const Handle& h);
+void batch_pbc_hvp_grad_carve(const Handle& h, double* base, int cap, BatchPbcHvpGradWs& w);
+// k_bhg_qtan over `rows` rows (cf_kernels_batch_hvp_grad.hip): qt [rows][3][N] from gam [rows][3][G]
+void launch_batch_hvp_qtan(Handle& h, int rows, const double* gam, double* qt);
+// one pass of nconf <= w.cap conformations x kv directions (nconf * kv <= min(gw.cap, kBatchMaxPass)
+// rows) on h.stream: at most nine launches.  boxes: device, [nconf][8] as launch_batch_pbc; pos, vec,
+// out_bar, vstride, first and grad as launch_batch_hvp_vjp
+void launch_batch_pbc_hvp_vjp(Handle& h, const BatchPbcWs& w, const BatchPbcHvpGradWs& gw, int nconf, int kv,
+                              const double* pos, const double* boxes, const double* vec, const double* out_bar,
+                              long vstride, bool first, double* grad);
+
 void check_hip(hipError_t e, const char* what);
 
 // ---- fp64 math helpers shared by the pair and grid kernels -------------------------

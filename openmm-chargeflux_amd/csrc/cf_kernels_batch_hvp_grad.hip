@@ -37,9 +37,6 @@
 
 namespace cf {
 
-// first geometry of term t: bonds and angles have one, waters three
-__device__ __forceinline__ int geom_start(int t, int nb, int na) { return t < nb + na ? t : nb + na + 3 * (t - nb - na); }
-
 // ---------------------------------------------------------------------------------
 // 1. geometry tangents: one lane per flattened (row, term).  The term's atoms carry (x, u, v, 0) as
 //    hyper-duals; the u, v and mixed parts of its geometries go to gam[row][0..3)[G].
@@ -359,6 +356,11 @@ static inline size_t ngeom(const Handle& h) { return (size_t)h.nb + (size_t)h.na
 
 int batch_hvp_grad_chunk() { return kHgKC; }
 
+void launch_batch_hvp_qtan(Handle& h, int rows, const double* gam, double* qt) {
+    hipLaunchKernelGGL(k_bhg_qtan, dim3(nblk(h.n, 256), rows), dim3(256), 0, h.stream, h.n, h.nb, h.na, (int)ngeom(h),
+                       h.term_par, h.qcsr_start, h.qcsr_slot, gam, qt);
+}
+
 size_t batch_hvp_grad_doubles_per_row(const Handle& h) {
     // the geometries' three tangents, (q^u, q^v, q^uv)[N], (g^u, g^v, g^uv)[N], g[N]
     return 3 * ngeom(h) + 7 * (size_t)h.n;
@@ -385,8 +387,7 @@ void launch_batch_hvp_vjp(Handle& h, const BatchWs& w, const BatchHvpGradWs& gw,
     if (h.nterms > 0)
         hipLaunchKernelGGL(k_bhg_geom, dim3(nblk((int64_t)rows * h.nterms, 256)), dim3(256), 0, h.stream, rows, kv, n,
                            h.nterms, h.nb, h.na, ngeo, h.term_idx, pos, vec, out_bar, vstride, gw.gam);
-    hipLaunchKernelGGL(k_bhg_qtan, dim3(nblk(n, 256), rows), dim3(256), 0, h.stream, n, h.nb, h.na, ngeo, h.term_par,
-                       h.qcsr_start, h.qcsr_slot, gw.gam, gw.qt);
+    launch_batch_hvp_qtan(h, rows, gw.gam, gw.qt);
     hipLaunchKernelGGL(k_bhg_pairs, dim3(nblk(n, kHgI), nconf * nchunks), dim3(256), 0, h.stream, n, kv, nchunks, h.ke,
                        pos, w.q, vec, out_bar, vstride, gw.qt, h.ex_start, h.ex_list, gw.g, gw.gt);
     hipLaunchKernelGGL(k_bhg_rows, dim3(nblk((int64_t)nconf * (n + h.nterms), 256)), dim3(256), 0, h.stream, nconf, kv, n,

@@ -171,6 +171,9 @@ SIGNATURES = [
     ("cf_compute_batch_periodic_hvp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, DP, C.c_int32, C.c_void_p,
                                                 C.c_void_p]),
     ("cf_compute_batch_periodic_hvp_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, C.c_int32, DP, DP]),
+    ("cf_compute_batch_periodic_hvp_vjp", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, DP, C.c_int32, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]),
+    ("cf_compute_batch_periodic_hvp_vjp_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, C.c_int32, DP, DP, DP]),
     ("cf_compute_batch_periodic_virial", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, DP, C.c_int, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cf_compute_batch_periodic_virial_host", C.c_int, [C.c_void_p, C.c_int32, DP, DP, C.c_int, DP, DP, DP, DP]),

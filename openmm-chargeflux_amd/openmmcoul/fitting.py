@@ -46,7 +46,8 @@ V_p = ke sum_a q_a / |r_p - x_a| of the charges after flux at M probe points per
     loss.backward()
 
 hvp() is cf_compute_batch_hvp forward and one cf_compute_batch_hvp_vjp backward: the Hessian-vector
-products H(x_b) v_bk and their closed-form parameter gradients.
+products H(x_b) v_bk and their closed-form parameter gradients.  With boxes= (a periodic kernel) it
+is cf_compute_batch_periodic_hvp and cf_compute_batch_periodic_hvp_vjp, H at fixed box.
 
 Convention (cf_compute_batch_lj_vjp): an atom with epsilon = 0 receives exactly 0 for its sigma and
 epsilon gradients.  The true derivative of sqrt(eps_i eps_j) is singular there; such an atom has no
@@ -257,14 +258,15 @@ class _EspFn(torch.autograd.Function):
 
 class _HvpFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, charges, bonds, angles, waters, positions, vectors):
+    def forward(ctx, model, charges, bonds, angles, waters, positions, vectors, boxes):
         params = tuple(t.detach().to("cpu", torch.float64).contiguous() for t in (charges, bonds, angles, waters))
         model._load(params)
         k = model.kernel
         model._before()
-        out = k.execute_batch_hvp_device(positions, vectors)
+        out = k.execute_batch_hvp_device(positions, vectors, boxes=boxes)
         model._after()
         ctx.model, ctx.params, ctx.loaded = model, params, model._loads
+        ctx.boxes = None if boxes is None else boxes.copy()   # the caller may change its array before backward
         ctx.inputs = (charges, bonds, angles, waters)
         ctx.save_for_backward(positions, vectors)
         return out
@@ -275,7 +277,7 @@ class _HvpFn(torch.autograd.Function):
         k = model.kernel
         positions, vectors = ctx.saved_tensors
         if not any(ctx.needs_input_grad[1:5]):
-            return (None,) * 7
+            return (None,) * 8
         if model._loads != ctx.loaded:   # another forward has changed the parameters since: put these back
             model._load(ctx.params)
             ctx.loaded = model._loads
@@ -283,12 +285,12 @@ class _HvpFn(torch.autograd.Function):
         counts = k.param_counts()
         grad = torch.empty((positions.shape[0], sum(counts)), dtype=torch.float64, device=positions.device)
         model._before()
-        k.execute_batch_hvp_vjp_device(positions, vectors, grad, cot)
+        k.execute_batch_hvp_vjp_device(positions, vectors, grad, cot, boxes=ctx.boxes)
         model._after()
         g = k.split_gradient(grad.sum(dim=0, keepdim=True), counts)
         out = [g[name][0].reshape(t.shape).to(t.device) if need else None
                for t, name, need in zip(ctx.inputs, ("charges", "bonds", "angles", "waters"), ctx.needs_input_grad[1:5])]
-        return (None, *out, None, None)
+        return (None, *out, None, None, None)
 
 
 class BatchedChargeFlux:
@@ -422,13 +424,15 @@ class BatchedChargeFlux:
             raise ValueError(f"points must have shape (B, M, 3), got {tuple(points.shape)}")
         return _EspFn.apply(self, charges, bonds, angles, waters, positions, points)
 
-    def hvp(self, charges, bonds, angles, waters, positions, vectors):
+    def hvp(self, charges, bonds, angles, waters, positions, vectors, boxes=None):
         """Hessian-vector products H(x_b) v_bk (B,K,N,3) of B conformations of a non-periodic system
         along the directions vectors (B,K,N,3) (float64, contiguous on the kernel's device) as a
         differentiable function of the four parameter tensors (arguments as __call__;
         cf_compute_batch_hvp forward, one cf_compute_batch_hvp_vjp with the incoming cotangent, summed
         over the conformations, in backward).  With v a normal mode e, d(e . H e)/d(parameters) is the
-        first-order shift of its squared frequency.  Neither positions nor vectors may require grad."""
+        first-order shift of its squared frequency.  Neither positions nor vectors may require grad.
+        boxes: for a periodic kernel, as __call__'s (a copy is kept for backward): H at fixed box,
+        cf_compute_batch_periodic_hvp forward and cf_compute_batch_periodic_hvp_vjp backward."""
         for t, name in ((charges, "charges"), (bonds, "bonds"), (angles, "angles"), (waters, "waters"),
                         (positions, "positions"), (vectors, "vectors")):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
@@ -437,4 +441,6 @@ class BatchedChargeFlux:
             raise ValueError("positions and vectors must not require grad: gradients with respect to them are not computed")
         if vectors.dim() != 4 or vectors.shape[0] != positions.shape[0] or tuple(vectors.shape[2:]) != tuple(positions.shape[1:]):   # before the parameters are loaded
             raise ValueError(f"vectors must have shape (B, K, N, 3), got {tuple(vectors.shape)}")
-        return _HvpFn.apply(self, charges, bonds, angles, waters, positions, vectors)
+        if boxes is not None:   # before the parameters are loaded
+            boxes = self.kernel._batch_boxes(boxes, positions.shape[0])
+        return _HvpFn.apply(self, charges, bonds, angles, waters, positions, vectors, boxes)

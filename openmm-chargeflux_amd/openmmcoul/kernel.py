@@ -766,12 +766,13 @@ class HipCalcCoulForceKernel:
                 out_bar, "out_bar", (nvec, self._n, 3), module) != nconf):
             raise ValueError(f"out_bar must be a float64 {kind.__name__} shaped like vectors")
 
-    def execute_batch_hvp_vjp_host(self, positions, vectors, out_bar=None):
+    def execute_batch_hvp_vjp_host(self, positions, vectors, out_bar=None, *, boxes=None):
         """Gradients of L = sum_k out_bar_k . (H v_k) with respect to the base charges and the flux
         parameters, per conformation (cf_compute_batch_hvp_vjp_host; non-periodic systems), H v the
         products execute_batch_hvp_host returns.  positions (B,N,3), vectors (B,K,N,3), out_bar
         (B,K,N,3): C-contiguous float64 numpy arrays; out_bar may be None (= zero) or vectors itself.
-        Returns the dict of execute_batch_vjp_host (split_gradient)."""
+        Returns the dict of execute_batch_vjp_host (split_gradient).
+        boxes (periodic systems, cf_compute_batch_periodic_hvp_vjp_host): as execute_batch_hvp_host."""
         if not isinstance(positions, np.ndarray):
             raise ValueError("positions must be a numpy array of shape (B, N, 3)")
         nconf = self._check_batch_array(positions, "positions", (self._n, 3))
@@ -779,14 +780,21 @@ class HipCalcCoulForceKernel:
         self._check_hvp_cotangent(out_bar, nconf, nvec, np, np.ndarray)
         counts = self.param_counts()
         flat = np.zeros((nconf, sum(counts)))
-        _cabi.check(self._lib.cf_compute_batch_hvp_vjp_host(self._h, nconf, _dp(positions), nvec, _dp(vectors),
-                                                            _dp(out_bar) if out_bar is not None else None,
+        bar = _dp(out_bar) if out_bar is not None else None
+        if boxes is not None:
+            b = self._batch_boxes(boxes, nconf)
+            _cabi.check(self._lib.cf_compute_batch_periodic_hvp_vjp_host(self._h, nconf, _dp(positions), _dp(b), nvec,
+                                                                         _dp(vectors), bar, _dp(flat)), self._lib)
+            return self.split_gradient(flat, counts)
+        _cabi.check(self._lib.cf_compute_batch_hvp_vjp_host(self._h, nconf, _dp(positions), nvec, _dp(vectors), bar,
                                                             _dp(flat)), self._lib)
         return self.split_gradient(flat, counts)
 
-    def execute_batch_hvp_vjp_device(self, positions, vectors, grad, out_bar=None):
+    def execute_batch_hvp_vjp_device(self, positions, vectors, grad, out_bar=None, *, boxes=None):
         """The same on torch tensors (float64, on the kernel's device, contiguous): grad (B,P) is
-        overwritten (split_gradient gives its views).  Asynchronous on the kernel's stream."""
+        overwritten (split_gradient gives its views).  Asynchronous on the kernel's stream.
+        boxes (periodic systems, cf_compute_batch_periodic_hvp_vjp): a numpy array in HOST memory here
+        too, read during the call."""
         import torch
         if not isinstance(positions, torch.Tensor):
             raise ValueError("positions must be a torch tensor of shape (B, N, 3)")
@@ -798,6 +806,11 @@ class HipCalcCoulForceKernel:
         if self._check_batch_array(grad, "grad", (sum(self.param_counts()),), torch) != nconf:
             raise ValueError(f"grad must hold {nconf} conformations")
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if boxes is not None:
+            b = self._batch_boxes(boxes, nconf)
+            _cabi.check(self._lib.cf_compute_batch_periodic_hvp_vjp(self._h, nconf, ptr(positions), _dp(b), nvec,
+                                                                    ptr(vectors), ptr(out_bar), ptr(grad)), self._lib)
+            return
         _cabi.check(self._lib.cf_compute_batch_hvp_vjp(self._h, nconf, ptr(positions), nvec, ptr(vectors), ptr(out_bar),
                                                        ptr(grad)), self._lib)
 
